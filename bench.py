@@ -24,15 +24,17 @@ units / max-over-ranks time):
               (split over the ranks); motifs of one width share each read of the k-mers
               (gfm_score_kmers_multi); unit = one (k-mer, motif) pair.
 
-Timing: W warm-up steps, then `--bursts` (5) bursts of EXACTLY K steps, each burst bracketed by a barrier +
-torch.cuda.synchronize() on both sides and reduced with MAX over the ranks; the line reports the MEDIAN
-burst.  Rank 0 prints ONE JSON line.  Beside the contract's fields it carries
+Timing: W warm-up steps, then EXACTLY K timed steps, split into `--bursts` (default 1) bursts of nearly equal
+length, each burst bracketed by a barrier + torch.cuda.synchronize() on both sides and reduced with MAX over the
+ranks; `ms_per_step` is the MEDIAN over the bursts of burst time / its steps.  Rank 0 prints ONE JSON line.
+With --dump-outputs DIR rank 0 also writes what the last timed step computed (see dump_outputs) as DIR/<name>.npy.
+Beside the contract's fields the line carries
   roofline            the score kernel alone: HIP events riding on its dispatch packets, sampled inside the timed
                       bursts; `peak` = 8 TB/s vendor, `peak_measured` = this device's bare interleaved stream of
                       the same byte mix (gfm_calibrate_stream), `frac_of_measured`; `traffic` from the committed PMC
                       passes (`traffic_source` says so);
   tail_ms             post kernel + [all-reduce] + q-table [+ selection on q] [+ gather], events on the tail stream;
-  rank_ms_per_step    every rank's own median burst; rccl_world = dist.get_world_size();
+  rank_ms_per_step    every rank's own median ms per step; rccl_world = dist.get_world_size();
   N = 1, default config only (each can be switched off):
   roofline_config3    >= 10 steps of the config-3 shard (1.25e8 windows generated on the device, `nt` stores: 477 MiB
                       of scores per launch, beyond any cache) -- also the 1-GPU point of the N > 1 curve
@@ -908,6 +910,81 @@ def extra_config_block(cfg, dev, rank, args, side, steps=12):
     return block
 
 
+# ---------------------------------------------------------------------------- --dump-outputs
+DUMP_LIMIT_BYTES = 64 << 20     # all files of one dump together
+DUMP_SAMPLE = 1 << 20           # rows kept of a longer output (a fixed, seeded sample)
+DUMP_SAMPLE_MULTI = 1 << 14     # the same per motif of config 5 (50 motifs)
+
+
+def _dump_sample(n, k, seed):
+    """Ascending indices of a fixed sample of k of n rows (all n rows when n <= k): the same for every run."""
+    if n <= k:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(np.random.default_rng(seed).choice(n, size=k, replace=False))
+
+
+def _sampled_hits(rows, scaled, qtable, k, seed):
+    """Hit rows (ascending) with their scaled scores and q-values; at most k of them, a fixed sample."""
+    i = _dump_sample(len(rows), k, seed)
+    return rows[i], scaled[i], qtable[scaled[i]]
+
+
+def scan_outputs(res, scores):
+    """What KmerScanner.collect hands its caller for the last timed step (configs 2-4), plus its score array:
+    hit rows ascending with their scaled scores and q-values, the q-table, the row count, and a fixed sample of the
+    int32 scores (scores_sample_rows says which rows)."""
+    import torch
+    idx = _dump_sample(int(scores.numel()), DUMP_SAMPLE, 1)
+    rows, scaled, qv = _sampled_hits(res["rows"], res["scaled"], res["qtable"], DUMP_SAMPLE, 2)
+    return {"hit_rows": rows, "hit_scaled_scores": scaled, "hit_qvalues": qv, "qtable": res["qtable"],
+            "n_scored": np.array([res["n_scored"]]), "n_hits": np.array([len(res["rows"])]),
+            "scores_sample_rows": idx, "scores_sample": scores[torch.from_numpy(idx).to(scores.device)].cpu().numpy()}
+
+
+def multi_outputs(scanners, groups, n_motifs, n):
+    """Config 5: per motif (index into the config's motif list) the hits of the last timed step (rows, scaled scores,
+    q-values; at most DUMP_SAMPLE_MULTI per motif, a fixed sample), the hit and row counts, and the scores of a fixed
+    sample of rows (scores_sample[motif, j] is the score of row scores_sample_rows[j])."""
+    import torch
+    from grafimo_amd.scan import HIT_SCORE_BITS
+    idx = _dump_sample(n, DUMP_SAMPLE_MULTI, 1)
+    d_idx = None
+    motif, rows, scaled, qv = [], [], [], []
+    n_hits, n_scored = np.zeros(n_motifs), np.zeros(n_motifs)
+    sample = np.zeros((n_motifs, len(idx)))
+    for w, sc in scanners.items():
+        hits, qtab, nrows = sc.hits.cpu().numpy(), sc.qtable.cpu().numpy(), sc.nrows.cpu().numpy()
+        for k, j in enumerate(groups[w]):
+            cnt = int(hits[k, 0])
+            if cnt > hits.shape[1] - 1:
+                raise OverflowError(f"motif {j}: {cnt} hits exceed the {hits.shape[1] - 1} entries the scanner holds")
+            packed = np.sort(hits[k, 1:1 + cnt])
+            r, s_, q = _sampled_hits(packed >> HIT_SCORE_BITS, packed & ((1 << HIT_SCORE_BITS) - 1), qtab[k],
+                                     DUMP_SAMPLE_MULTI, 2 + j)
+            motif.append(np.full(len(r), j))
+            rows.append(r)
+            scaled.append(s_)
+            qv.append(q)
+            n_hits[j], n_scored[j] = cnt, nrows[k]
+            if d_idx is None:
+                d_idx = torch.from_numpy(idx).to(sc.scores[k].device)
+            sample[j] = sc.scores[k][d_idx].cpu().numpy()
+    return {"hit_motif": np.concatenate(motif), "hit_rows": np.concatenate(rows), "hit_scaled_scores": np.concatenate(scaled),
+            "hit_qvalues": np.concatenate(qv), "n_hits": n_hits, "n_scored": n_scored,
+            "scores_sample_rows": idx, "scores_sample": sample}
+
+
+def dump_outputs(out_dir, arrays):
+    """DIR/<name>.npy for every array, as float64 (exact for every integer output here: all are below 2**53)."""
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise RuntimeError(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -915,7 +992,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--config", type=int, choices=[2, 3, 4, 5], default=None,
                     help="BASELINE.json config (default: 2 on one GPU, 3 = its per-GPU shard on several)")
-    ap.add_argument("--bursts", type=int, default=5, help="timed bursts of --steps steps; the median is reported")
+    ap.add_argument("--bursts", type=int, default=1,
+                    help="split the --steps timed steps into this many bursts; the median ms per step is reported")
     ap.add_argument("--rows", type=int, default=None, help="override the rows per GPU (diagnostics)")
     ap.add_argument("--threshold", type=float, default=1e-4)
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -936,7 +1014,7 @@ def main():
                          "one rank (exercises the N > 1 code path on a 1-GPU box)")
     ap.add_argument("--event-every", type=int, default=None,
                     help="time the score kernel of every n-th step with a hipEvent pair on its dispatch "
-                         "(default: every 8th, more often when the run is short, so that at least ~24 launches are timed)")
+                         "(default: every 8th, more often when the run is short, so that at least ~6 launches are timed)")
     ap.add_argument("--no-candidates", action="store_true",
                     help="config 4: select on the q-value threshold by a pass over every score instead of "
                          "filtering the p < t candidates the score kernel collects (measurement aid)")
@@ -946,7 +1024,11 @@ def main():
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher / process-group plumbing only (gloo, no GPU, nothing measured): the CPU tests use it")
     ap.add_argument("--dry-run-fail-rank", type=int, default=None, help="with --dry-run: this rank exits with code 3")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float64, <= 64 MB in all)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))       # this process never touches a GPU
@@ -1075,14 +1157,17 @@ def run_rank(args, cfg, rank, local_rank, world, mots, ctcf, n, host_batch, on_q
     fence()
     if cfg != 5 and use_dist:
         scanner.size_gather()          # the per-step gather moves what is hit, not the whole hit buffer
-    every = max(1, args.event_every) if args.event_every else max(1, min(8, args.bursts * args.steps // 24))
+    every = max(1, args.event_every) if args.event_every else max(1, min(8, args.steps // 6))
     for d in dms:
-        d.profile_enable(min(1024, max(16, args.bursts * args.steps // every + 1)), every=every)
-    burst_s, own_s = [], []
-    for _ in range(max(1, args.bursts)):
+        d.profile_enable(min(1024, max(16, args.steps // every + 1)), every=every)
+    # the --steps timed steps, split into --bursts bursts of (nearly) equal length
+    n_bursts = min(max(1, args.bursts), args.steps)
+    burst_steps = [args.steps // n_bursts + (b < args.steps % n_bursts) for b in range(n_bursts)]
+    burst_s, own_s = [], []           # seconds per burst (MAX over ranks) and this rank's own
+    for k in burst_steps:
         fence()
         t0 = time.perf_counter()
-        for _ in range(args.steps):
+        for _ in range(k):
             last = step(it)
             it += 1
         fence()
@@ -1091,14 +1176,15 @@ def run_rank(args, cfg, rank, local_rank, world, mots, ctcf, n, host_batch, on_q
         if use_dist:
             dist.all_reduce(el, op=dist.ReduceOp.MAX)
         burst_s.append(float(el.item()))
+    step_s = float(np.median([b / k for b, k in zip(burst_s, burst_steps)]))     # seconds per timed step
     kernel_ms = [d.profile_read() for d in dms]
     tail_ms = dms[0].profile_read_tail() if cfg != 5 else np.empty(0, np.float32)
     for d in dms:
         d.profile_enable(0)
     if cfg != 5:
         scanner.profile_tail = False
-    # every rank's own median burst -> rank 0
-    mine = torch.tensor([1e3 * float(np.median(own_s)) / args.steps], dtype=torch.float64, device=dev)
+    # every rank's own median ms per step -> rank 0
+    mine = torch.tensor([1e3 * float(np.median([b / k for b, k in zip(own_s, burst_steps)]))], dtype=torch.float64, device=dev)
     rank_ms = [mine.clone() for _ in range(world)]
     if use_dist and world > 1:
         dist.all_gather(rank_ms, mine)
@@ -1129,6 +1215,9 @@ def run_rank(args, cfg, rank, local_rank, world, mots, ctcf, n, host_batch, on_q
         exp, _ = orc.score_kmers_table(km, mots[0]["sm"], pt, mots[0]["min_val"])
         assert np.array_equal(last.scores[:len(km)].cpu().numpy(), exp), "scores differ from the oracle"
     assert n_hits > 0
+    if args.dump_outputs and rank == 0:      # before the blocks below run further steps on these buffers
+        dump_outputs(args.dump_outputs, multi_outputs(scanners, groups, len(mots), n) if cfg == 5
+                     else scan_outputs(res, last.scores[:n]))
 
     extras = {}
     if use_dist and cfg in (2, 3) and not args.no_extras:
@@ -1179,7 +1268,7 @@ def run_rank(args, cfg, rank, local_rank, world, mots, ctcf, n, host_batch, on_q
             extras["roofline_noscore"] = {"error": f"{type(e).__name__}: {e}"}
         # (b) sustained: back-to-back steps for >= sustained_s seconds, one timing event per 100 steps
         per = 100
-        blocks = max(2, int(args.sustained_s / (np.median(burst_s) / args.steps) / per) + 1)
+        blocks = max(2, int(args.sustained_s / step_s / per) + 1)
         evs = [torch.cuda.Event(enable_timing=True) for _ in range(blocks + 1)]
         fence()
         main_stream = torch.cuda.current_stream(dev)
@@ -1288,9 +1377,8 @@ def run_rank(args, cfg, rank, local_rank, world, mots, ctcf, n, host_batch, on_q
             e2e[name] = e2e_block(tmp, rows, ctcf.width, dms[0])
 
     if rank == 0:
-        elapsed = float(np.median(burst_s))
-        ms_per_step = 1e3 * elapsed / args.steps
-        value = units_per_step * world * args.steps / elapsed
+        ms_per_step = 1e3 * step_s
+        value = units_per_step * world / step_s
         if cfg == 5:      # a step launches one batched kernel per group of <= 3 same-width motifs: sum of their means
             k_ms = float(sum(float(np.mean(k)) for k in kernel_ms if len(k)))
             timed = int(sum(len(k) for k in kernel_ms))
@@ -1404,8 +1492,10 @@ def run_rank(args, cfg, rank, local_rank, world, mots, ctcf, n, host_batch, on_q
                 "oracle_checked_rows": checked_rows if cfg != 5 else checked_rows * len(mots),
                 "input_buffers_rotated": rotate,
                 "bursts": len(burst_s),
+                "burst_steps": burst_steps,
                 "burst_ms": [round(1e3 * b, 4) for b in burst_s],
-                "timing": "median burst of `steps` steps, each burst barrier + synchronize bracketed, MAX over ranks",
+                "timing": "`steps` timed steps in `bursts` bursts, each burst barrier + synchronize bracketed, MAX over ranks; "
+                          "ms_per_step = median over the bursts of burst time / its steps",
                 "sharding": (f"regions split over {world} rank(s); all-reduce(score histogram) + gather(hit entries, "
                              f"sized from the observed hit counts) per step") if world > 1 else "single GPU",
                 "fused": fused_cfg,

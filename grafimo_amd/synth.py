@@ -176,7 +176,13 @@ def make_device_kmers(n: int, width: int, pwm_probs: np.ndarray, seed: int, devi
     for a in range(0, k, 1_000_000):
         u = torch.rand((min(k, a + 1_000_000) - a, W), generator=g, device=device, dtype=torch.float64)
         code = (u[:, None, :] > cdf[None, :, :]).sum(1).clamp(max=3)
-        out[rows[a:a + 1_000_000]] = alpha[code]
+        # a row drawn more than once takes its last draw, as on the host: a device write through repeated indices
+        # leaves the winner unspecified, and the same seed must give the same k-mers on every run
+        r = rows[a:a + 1_000_000]
+        uniq, inv = torch.unique(r, return_inverse=True)
+        last = torch.full((len(uniq),), -1, dtype=torch.int64, device=device).scatter_reduce(
+            0, inv, torch.arange(len(r), device=device), "amax")
+        out[r[last]] = alpha[code[last]]
     if n >= 1000:
         out[torch.randint(0, n, (n // 1000,), generator=g, device=device), W // 2] = ord("N")
     return out

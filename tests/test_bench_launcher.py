@@ -107,3 +107,32 @@ def test_a_stage_that_fails_on_one_rank_stops_every_rank_together(tmp_path):
         assert g["after"] == 3                                               # 1 + 2: the next collective is in step
     assert got[1]["res"]["b"] == {"error": "RuntimeError: rank 1 cannot"}
     assert got[0]["res"]["b"] == {"error": "another rank failed in this stage"}
+
+
+def test_dump_outputs_is_a_fixed_float64_sample_under_the_limit(tmp_path):
+    """--dump-outputs without a GPU: a score array longer than the sample keeps the same seeded rows on every call, every
+    file is float64 and equals what it was made from, and a dump beyond 64 MB is refused instead of written."""
+    import numpy as np
+    import pytest
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    n = bench.DUMP_SAMPLE + 12345
+    scores = torch.arange(n, dtype=torch.int32) % 977
+    rows = np.arange(0, 3 * n, 3, dtype=np.int64)[: bench.DUMP_SAMPLE + 7]
+    res = {"rows": rows, "scaled": (rows % 977).astype(np.int32), "qtable": np.linspace(0.0, 1.0, 977), "n_scored": n}
+    a, b = bench.scan_outputs(res, scores), bench.scan_outputs(res, scores)
+    bench.dump_outputs(str(tmp_path / "d"), a)
+    idx = a["scores_sample_rows"]
+    assert len(idx) == bench.DUMP_SAMPLE and np.all(np.diff(idx) > 0) and idx[-1] < n
+    assert len(a["hit_rows"]) == bench.DUMP_SAMPLE and a["n_hits"][0] == len(rows) and a["n_scored"][0] == n
+    for name, v in a.items():
+        got = np.load(tmp_path / "d" / f"{name}.npy")
+        assert got.dtype == np.float64 and np.array_equal(got, np.asarray(v, dtype=np.float64)), name
+        assert np.array_equal(v, b[name]), name
+    assert np.array_equal(a["scores_sample"], scores.numpy()[idx])
+    assert np.array_equal(a["hit_qvalues"], res["qtable"][a["hit_scaled_scores"]])
+    assert sum(f.stat().st_size for f in (tmp_path / "d").iterdir()) <= bench.DUMP_LIMIT_BYTES
+    with pytest.raises(RuntimeError):
+        bench.dump_outputs(str(tmp_path / "big"), {"x": np.zeros(bench.DUMP_LIMIT_BYTES // 8 + 1)})
+    assert not (tmp_path / "big").exists()

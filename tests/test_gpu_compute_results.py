@@ -768,6 +768,36 @@ def test_bench_distributed_path_on_one_gpu_with_reserved_cus():
 
 
 @pytest.mark.timeout(900)
+def test_bench_steps_and_dumped_outputs(tmp_path):
+    """--steps K times exactly K steps (split over --bursts), and --dump-outputs writes the last timed step's results:
+    two runs with the same arguments dump the same arrays, and the arrays agree with each other and the result line."""
+    import json
+    import subprocess
+    import sys
+    from conftest import ROOT
+    recs = []
+    for run in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "3", "--rows", "4000000",
+                            "--steps", "7", "--warmup", "2", "--bursts", "2", "--no-cpu-baseline", "--no-e2e", "--no-extras",
+                            "--dump-outputs", str(tmp_path / run)], capture_output=True, text=True, timeout=800)
+        assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
+        recs.append(json.loads([ln for ln in r.stdout.splitlines() if ln.strip().startswith("{")][-1]))
+    rec = recs[0]
+    assert rec["steps"] == 7 and rec["config"]["burst_steps"] == [4, 3] and rec["ms_per_step"] > 0
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(os.listdir(tmp_path / "b")) and "hit_rows.npy" in names and "scores_sample.npy" in names
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in names) <= 64 << 20
+    got = {f[:-4]: np.load(tmp_path / "a" / f) for f in names}
+    for f in names:
+        assert got[f[:-4]].dtype == np.float64
+        assert np.array_equal(got[f[:-4]], np.load(tmp_path / "b" / f)), f
+    assert got["n_scored"][0] == 4_000_000 and got["n_hits"][0] == rec["config"]["hits_last_step"] > 0
+    assert len(got["hit_rows"]) == got["n_hits"][0] and np.all(np.diff(got["hit_rows"]) > 0)
+    assert np.array_equal(got["hit_qvalues"], got["qtable"][got["hit_scaled_scores"].astype(np.int64)])
+    assert len(got["scores_sample"]) == len(got["scores_sample_rows"]) == 1 << 20
+
+
+@pytest.mark.timeout(900)
 def test_bench_product_paths_block_under_a_process_group():
     """What `bench.py --gpus N` adds at N > 1 -- the fused graph path (a rank uploads its shard of the graph) and the streamed
     scan under the run's process group -- driven with a one-rank RCCL group on the test box's one GPU: both blocks report rows

@@ -344,3 +344,28 @@ def test_lease_key_fingerprint_of_a_score_distribution():
             assert _fingerprint(c) != f
     assert len(seen) == 201
     assert _fingerprint(np.zeros(0)) == (0, 0, 0) and _fingerprint(a[:1000]) != _fingerprint(a[:1001])
+
+
+def test_device_kmer_generator_gives_a_row_drawn_twice_its_last_draw():
+    """synth.make_device_kmers (configs 3-5 of bench.py) plants PWM samples on rows drawn with repetition: a repeated row must
+    take its LAST draw, as a sequential loop over the same draws would, so that one seed gives the same k-mers on every run
+    (a device write through repeated indices leaves the winner unspecified).  Run here on the CPU device."""
+    import torch
+    from grafimo_amd import synth
+    n, W, seed = 200_000, 19, 11
+    probs = np.random.default_rng(3).dirichlet(np.ones(4), W).T
+    got = synth.make_device_kmers(n, W, probs, seed, torch.device("cpu")).numpy()
+    g = torch.Generator()
+    g.manual_seed(seed)
+    alpha = np.frombuffer(b"ACGT", np.uint8)
+    exp = alpha[torch.multinomial(torch.tensor(synth.BG_NT / synth.BG_NT.sum()), n * W, replacement=True,
+                                  generator=g).view(n, W).numpy()]
+    rows = torch.randint(0, n, (n // 100,), generator=g).numpy()
+    cdf = torch.tensor(np.cumsum(probs / probs.sum(0, keepdims=True), axis=0))
+    u = torch.rand((len(rows), W), generator=g, dtype=torch.float64)
+    code = (u[:, None, :] > cdf[None]).sum(1).clamp(max=3).numpy()
+    assert len(np.unique(rows)) < len(rows)                  # the case in question occurs
+    for r, c in zip(rows, code):
+        exp[r] = alpha[c]
+    exp[torch.randint(0, n, (n // 1000,), generator=g).numpy(), W // 2] = ord("N")
+    assert np.array_equal(got, exp)
