@@ -52,7 +52,10 @@ PROTOTYPES = {
     "gfm_compute_log_odds": (c_int, [c_void_p, c_int, c_void_p, c_void_p]),
     "gfm_scale_pwm": (c_int, [c_void_p, c_int, c_void_p, P(c_int), P(c_int), P(c_int), P(c_double)]),
     "gfm_comp_pval_mat": (c_int, [c_void_p, c_int, c_void_p, c_void_p]),
+    "gfm_comp_pval_mat_many": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "gfm_motif_create": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_double, c_void_p, P(c_void_p)]),
+    "gfm_motif_create_many": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                      c_void_p]),
     "gfm_motif_destroy": (None, [c_void_p]),
     "gfm_motif_width": (c_int, [c_void_p]),
     "gfm_motif_table_len": (c_int, [c_void_p]),

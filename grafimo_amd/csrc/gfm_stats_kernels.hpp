@@ -8,6 +8,21 @@
 namespace {
 
 // ---------------------------------------------------------------------------------------
+// One motif's share of the DP and tail-table launches: workgroup blockIdx.x serves jobs[blockIdx.x].  A motif set is
+// ONE launch of each kernel (one workgroup per motif); a single motif is the case of one job.  The score matrix and the
+// cumulative windows are ints and the background doubles of one packed upload (offsets into it); the rows, the pmf and
+// the tail table are device pointers of the motif's own.
+struct DpJob {
+    long long sm;     // ints: score matrix [4][W], rows A, C, G, T
+    long long cum;    // ints: cum_lo [W] | cum_hi [W], the reachable window after each position
+    long long bg;     // doubles: background [4]
+    int W, L, lo, hi; // lo, hi: the reachable range after the last position
+    double *buf;      // the DP's two rows, 2 L doubles
+    double *pmf;      // L doubles
+    double *ptable;   // L doubles (ptable_kernel only)
+};
+
+// ---------------------------------------------------------------------------------------
 // pvalue_dp_kernel: score-distribution DP of comp_pval_mat (motif_processing.pyx:552-603),
 // one 1024-thread workgroup per motif, gather form:
 //   cur[t] = sum over n in A,C,G,T of prev[t - sm[n][pos]] * bg[n]
@@ -15,17 +30,22 @@ namespace {
 // (__dmul_rn/__dadd_rn: no FMA contraction) and the reference's `> 0` support test.  The
 // reference scatters, but each (n, idx) pair hits a distinct target once per n and n runs
 // outermost, so per target the additions arrive in exactly this order: bit-identical.
-// Rows ping-pong in global memory (they live in L2: 2*L*8 B <= 1 MB); only the reachable
-// window [cum_lo[pos], cum_hi[pos]] of a row is computed or read.
+// Rows ping-pong in global memory (one motif's 2*L*8 B <= 1 MB sit in L2; a set's in the
+// Infinity Cache); only the reachable window [cum_lo[pos], cum_hi[pos]] of a row is computed or read.
 constexpr int kDpThreads = 1024;
 
 __global__ void __launch_bounds__(kDpThreads)
-pvalue_dp_kernel(const int *__restrict__ sm, const double *__restrict__ bg, int W, int L,
-                 const int *__restrict__ cum_lo, const int *__restrict__ cum_hi,
-                 double *__restrict__ buf, double *__restrict__ pmf_out)
+pvalue_dp_kernel(const DpJob *__restrict__ jobs, const int *__restrict__ ints, const double *__restrict__ dbls)
 {
-    double *cur = buf;
-    double *prev = buf + L;
+    const DpJob job = jobs[blockIdx.x];
+    const int W = job.W, L = job.L;
+    const int *__restrict__ sm = ints + job.sm;
+    const int *__restrict__ cum_lo = ints + job.cum;
+    const int *__restrict__ cum_hi = cum_lo + W;
+    const double *__restrict__ bg = dbls + job.bg;
+    double *__restrict__ pmf_out = job.pmf;
+    double *cur = job.buf;
+    double *prev = job.buf + L;
     const int tid = threadIdx.x;
     {   // position 0 (motif_processing.pyx:593-594)
         const int l0 = cum_lo[0], h0 = cum_hi[0];
@@ -68,7 +88,7 @@ pvalue_dp_kernel(const int *__restrict__ sm, const double *__restrict__ bg, int 
 constexpr int kScanThreads = 1024;
 
 // p_table[s] = (sum_{t>=s} pmf[t]) / (sum_t pmf[t])   -- O(1) form of
-// `pval_mat[score:].sum() / pval_mat.sum()` (score_sequences.py:390-391).
+// `pval_mat[score:].sum() / pval_mat.sum()` (score_sequences.py:390-391), one workgroup per job.
 // Blocked suffix sum that stays EXACTLY monotone: thread t sums its contiguous segment top-down
 // (local running sums L_j), one lane chains the 1024 segment totals top-down (carry c_t), and
 // suffix[j] = c_t + L_j.  fl(c + L) is monotone in L, and at a segment's bottom c_t + L = c_t + s_t
@@ -77,8 +97,12 @@ constexpr int kScanThreads = 1024;
 // (A scan with mixed association orders broke monotonicity by 1 ulp; a fully sequential chain
 // took 0.5 ms.)
 __global__ void __launch_bounds__(kScanThreads)
-ptable_kernel(const double *__restrict__ pmf, int L, int lo, int hi, double *__restrict__ ptable)
+ptable_kernel(const DpJob *__restrict__ jobs)
 {
+    const DpJob job = jobs[blockIdx.x];
+    const double *__restrict__ pmf = job.pmf;
+    double *__restrict__ ptable = job.ptable;
+    const int L = job.L, lo = job.lo, hi = job.hi;
     __shared__ double carry[kScanThreads];
     __shared__ double tot_s;
     const int tid = threadIdx.x;

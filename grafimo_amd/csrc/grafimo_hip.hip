@@ -138,51 +138,77 @@ void cumulative_windows(const int64_t *sm, int W, std::vector<int> &lo, std::vec
     }
 }
 
-int validate_matrix(const int64_t *sm, int W)
+// the score matrix of motif `i` of a set
+int validate_matrix(const int64_t *sm, int W, int i)
 {
-    if (!sm) return fail(GFM_ERR_INVALID, "score matrix is NULL");
+    if (!sm) return fail(GFM_ERR_INVALID, "motif %d: score matrix is NULL", i);
     if (W < 1 || W > GFM_MAX_WIDTH)
-        return fail(GFM_ERR_INVALID, "motif width %d outside [1, %d]", W, GFM_MAX_WIDTH);
-    for (int i = 0; i < 4 * W; ++i)
-        if (sm[i] < 0 || sm[i] > kRange)
-            return fail(GFM_ERR_INVALID, "scaled score %lld outside [0, %d]", (long long)sm[i], kRange);
+        return fail(GFM_ERR_INVALID, "motif %d: motif width %d outside [1, %d]", i, W, GFM_MAX_WIDTH);
+    for (int k = 0; k < 4 * W; ++k)
+        if (sm[k] < 0 || sm[k] > kRange)
+            return fail(GFM_ERR_INVALID, "motif %d: scaled score %lld outside [0, %d]", i, (long long)sm[k], kRange);
     return GFM_OK;
 }
 
-// runs the DP for one motif on the current device; d_pmf receives L doubles
-// device scratch of one DP run: [4W + W + W ints | pad to 8 | 4 + 2L doubles]
-size_t dp_scratch_bytes(int W)
-{
-    const size_t L = (size_t)kRange * W + 1;
-    return ((sizeof(int) * 6 * (size_t)W + 7) & ~(size_t)7) + sizeof(double) * (4 + 2 * L);
-}
+size_t align256(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
 
-// runs the DP for one motif on the current device; d_pmf receives L doubles.  `scratch`
-// (dp_scratch_bytes, 8-byte aligned) saves the temporaries' allocations; nullptr = allocate here.
-int run_dp(const int64_t *sm, int W, const double *bg, double *d_pmf, hipStream_t st, void *scratch = nullptr)
-{
-    const int L = kRange * W + 1;
-    std::vector<int> lo, hi, ints(6 * (size_t)W);
-    cumulative_windows(sm, W, lo, hi);
-    for (int i = 0; i < 4 * W; ++i) ints[(size_t)i] = (int)sm[i];
-    std::copy(lo.begin(), lo.end(), ints.begin() + 4 * W);
-    std::copy(hi.begin(), hi.end(), ints.begin() + 5 * W);
-    DevBuf<unsigned char> own;
-    if (!scratch) {
-        HIP_TRY(own.alloc(dp_scratch_bytes(W)));
-        scratch = own.p;
+// The DP / tail-table jobs of a motif set and their ONE packed upload [jobs | ints | doubles] (gfm_stats_kernels.hpp):
+// per motif the score matrix [4][W] and the cumulative windows cum_lo [W] | cum_hi [W] as ints, the background [4] as
+// doubles.  The device pointers of a job (rows, pmf, tail table) are the caller's to fill in.
+struct DpPack {
+    std::vector<DpJob> jobs;
+    std::vector<int> ints;
+    std::vector<double> dbls;
+
+    DpJob &add(const int64_t *sm, int W, const double *bg)
+    {
+        std::vector<int> lo, hi;
+        cumulative_windows(sm, W, lo, hi);
+        DpJob j{};
+        j.sm = (long long)ints.size();
+        for (int i = 0; i < 4 * W; ++i) ints.push_back((int)sm[i]);
+        j.cum = (long long)ints.size();
+        ints.insert(ints.end(), lo.begin(), lo.end());
+        ints.insert(ints.end(), hi.begin(), hi.end());
+        j.bg = (long long)dbls.size();
+        dbls.insert(dbls.end(), bg, bg + 4);
+        j.W = W;
+        j.L = kRange * W + 1;
+        j.lo = lo[W - 1];
+        j.hi = hi[W - 1];
+        jobs.push_back(j);
+        return jobs.back();
     }
-    int *d_int = static_cast<int *>(scratch);
-    double *d_dbl = reinterpret_cast<double *>(static_cast<unsigned char *>(scratch) +
-                                               ((sizeof(int) * 6 * (size_t)W + 7) & ~(size_t)7));
-    HIP_TRY(hipMemcpyAsync(d_int, ints.data(), sizeof(int) * ints.size(), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(d_dbl, bg, sizeof(double) * 4, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(pvalue_dp_kernel, dim3(1), dim3(kDpThreads), 0, st, d_int, d_dbl, W, L, d_int + 4 * W,
-                       d_int + 5 * W, d_dbl + 4, d_pmf);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(st));   // the host vectors and the temporaries go away on return
-    return GFM_OK;
-}
+    size_t ints_at() const { return align256(sizeof(DpJob) * jobs.size()); }
+    size_t dbls_at() const { return ints_at() + align256(sizeof(int) * ints.size()); }
+    size_t bytes() const { return dbls_at() + sizeof(double) * dbls.size(); }
+    // the host image of the upload (it must outlive the asynchronous copy that reads it)
+    std::vector<unsigned char> image() const
+    {
+        std::vector<unsigned char> img(bytes(), 0);
+        std::memcpy(img.data(), jobs.data(), sizeof(DpJob) * jobs.size());
+        std::memcpy(img.data() + ints_at(), ints.data(), sizeof(int) * ints.size());
+        std::memcpy(img.data() + dbls_at(), dbls.data(), sizeof(double) * dbls.size());
+        return img;
+    }
+    // enqueues the DP of jobs [0, n_dp) and, when `tails`, the tail tables of every job: one launch of each kernel.
+    // `d` holds image() (already enqueued on st).
+    int launch(const unsigned char *d, int n_dp, bool tails, hipStream_t st) const
+    {
+        const DpJob *d_jobs = reinterpret_cast<const DpJob *>(d);
+        if (n_dp > 0) {
+            hipLaunchKernelGGL(pvalue_dp_kernel, dim3((unsigned)n_dp), dim3(kDpThreads), 0, st, d_jobs,
+                               reinterpret_cast<const int *>(d + ints_at()),
+                               reinterpret_cast<const double *>(d + dbls_at()));
+            HIP_TRY(hipGetLastError());
+        }
+        if (tails && !jobs.empty()) {
+            hipLaunchKernelGGL(ptable_kernel, dim3((unsigned)jobs.size()), dim3(kScanThreads), 0, st, d_jobs);
+            HIP_TRY(hipGetLastError());
+        }
+        return GFM_OK;
+    }
+};
 
 // score_quad_kernel<W, MM> is instantiated in score_quad_tu.hip: eight translation units of sixteen widths and one
 // MM each (compiled side by side: one unit with all of them took four minutes).  `args` = ScoreArgs<mm>.
@@ -513,22 +539,244 @@ GFM_API int gfm_scale_pwm(const double *lo, int W, int64_t *sm, int *min_val, in
     return GFM_OK;
 }
 
+namespace {
+
+// The checks of motif `i` of a set, made for every motif before anything touches the device (min_val / scale: NULL
+// when the call has none)
+int validate_motif(int i, const int64_t *sm, int W, const double *bg, const int *min_val, const int *scale)
+{
+    int rc = validate_matrix(sm, W, i);
+    if (rc) return rc;
+    if (scale && *scale <= 0) return fail(GFM_ERR_INVALID, "motif %d: scale must be a positive integer", i);
+    if (min_val) {   // min_val indexes the histogram and the tables on the device: it must be the matrix minimum
+        // (Motif.min_val, motif_ops.py:1106), the score of a k-mer holding N (score_sequences.py:376-378)
+        int64_t mn = sm[0];
+        for (int k = 1; k < 4 * W; ++k) mn = std::min(mn, sm[k]);
+        if ((int64_t)*min_val != mn)
+            return fail(GFM_ERR_INVALID, "motif %d: min_val %d is not the minimum of the score matrix (%lld)", i, *min_val,
+                        (long long)mn);
+    }
+    for (int n = 0; n < 4; ++n)
+        if (!(bg[n] > 0)) return fail(GFM_ERR_ASSERT, "motif %d: assert bg > 0 (motif_processing.pyx:592)", i);
+    return GFM_OK;
+}
+
+// histogram bins the score kernel's LDS leaves beside the tables and strips of 16 / 8 waves (-1 for the N bin)
+void score_rooms(int W, long long *room16, long long *room8)
+{
+    *room16 = ((long long)kMaxLdsBytes - (long long)quad_fixed_lds(W, kWavesPerWG)) / (long long)sizeof(unsigned) - 1;
+    *room8 = ((long long)kMaxLdsBytes - (long long)quad_fixed_lds(W, kWavesPerWG / 2)) / (long long)sizeof(unsigned) - 1;
+}
+
+// The host side of a new handle and its ONE device allocation (a motif set creates hundreds of these; ~20 hipMalloc /
+// hipFree pairs per motif were most of the creation time).  The pair tables' uploads are enqueued on the null stream
+// from `tab` / `ftab`, which must outlive them.  *d_rows: the DP's two rows (2 L doubles) in the slab.  On failure
+// the caller destroys `m`.
+int motif_alloc(gfm_motif *m, const int64_t *sm, int W, const double *bg, int min_val, int scale, double offset,
+                std::vector<uint16_t> &tab, std::vector<unsigned> &ftab, double **d_rows)
+{
+    m->W = W;
+    m->L = kRange * W + 1;
+    m->min_val = min_val;
+    m->scale = scale;
+    m->offset = offset;
+    m->ndw = (W + 3) / 4;
+    m->sm.assign(sm, sm + 4 * W);
+    std::memcpy(m->bg, bg, sizeof m->bg);
+    std::vector<int> clo, chi;
+    cumulative_windows(sm, W, clo, chi);
+    m->lo = clo[W - 1];
+    m->hi = chi[W - 1];
+    m->nb = m->hi - m->lo + 1;
+
+    HIP_TRY(hipGetDevice(&m->device));
+    {   // compute-unit count of the device, queried once per process (hipGetDeviceProperties is slow)
+        static std::atomic<int> cu_of[64];
+        int cu = cu_of[m->device & 63].load(std::memory_order_acquire);
+        if (cu == 0) {
+            HIP_TRY(hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, m->device));
+            if (cu <= 0) cu = 256;
+            cu_of[m->device & 63].store(cu, std::memory_order_release);
+        }
+        m->n_cu = cu;
+    }
+    if (const char *e = std::getenv("GRAFIMO_RESERVE_CUS")) m->reserve_cus = std::max(0, std::min(atoi(e), m->n_cu - 1));
+
+    // LDS lookup tables: [2*ndw base pairs][8 x 8 codes] uint16, code = (ascii >> 1) & 7
+    // (A 0, C 1, T 2, G 3; 4..7 invalid), index = code(first) + 8 * code(second).
+    // A valid pair holds sm[first][2p] + sm[second][2p+1]; a pair with an invalid code holds
+    // kPoison; a position >= W contributes 0 and accepts any code.
+    tab.assign((size_t)2 * m->ndw * 64, 0);
+    auto base_score = [&](int pos, int code, bool *bad) -> unsigned {
+        if (pos >= W) return 0u;
+        static const int nuc_of_code[4] = {0, 1, 3, 2};  // code 2 = T (row 3), code 3 = G (row 2)
+        if (code > 3) { *bad = true; return 0u; }
+        return (unsigned)sm[nuc_of_code[code] * W + pos];
+    };
+    for (int pr = 0; pr < 2 * m->ndw; ++pr)
+        for (int c1 = 0; c1 < 8; ++c1)
+            for (int c0 = 0; c0 < 8; ++c0) {
+                bool bad = false;
+                const unsigned v = base_score(2 * pr, c0, &bad) + base_score(2 * pr + 1, c1, &bad);
+                tab[(size_t)pr * 64 + c0 + 8 * c1] = (uint16_t)(bad ? kPoison : v);
+            }
+    // score-kernel LDS plan: pair tables | wave strips + hit queues | histogram window (+1 N bin).  With 16 waves
+    // the strips leave room16 bins; a reachable range that does not fit gets the whole LDS of an 8-wave
+    // workgroup (half the strips) unless a 16-wave window still covers practically all of the background
+    // mass (decided in motif_finish, once the tail table exists).
+    long long room16, room8;
+    score_rooms(W, &room16, &room8);
+    if (room8 < 256) return fail(GFM_ERR_INVALID, "no LDS left for a histogram window at width %d", W);
+    // (batched launches carry bigger tables and more hit queues: their windows are never larger than these)
+    m->part_nb = (int)std::min<long long>(m->nb, std::max(room16, room8));
+    m->max_slabs = m->n_cu * kWGsPerCU;
+    m->sel_slabs = 4 * m->n_cu;
+
+    size_t slab_bytes = 0;
+    auto carve = [&](size_t bytes) { const size_t at = slab_bytes; slab_bytes += align256(bytes); return at; };
+    const size_t o_tab = carve(tab.size() * sizeof(uint16_t));
+    // the fused extraction -> scoring kernels' table (gfm_graph_fused.hpp): ONE lookup per base serves both strands -- the
+    // reverse complement holds comp(base j) at position W-1-j; code 2 = T (row 3), code 3 = G (row 2); codes 4..7 hold 0
+    ftab.assign((size_t)W * 8, 0u);
+    {
+        static const int row_of_code[4] = {0, 1, 3, 2};
+        for (int j = 0; j < W; ++j)
+            for (int c = 0; c < 4; ++c) {
+                const unsigned fwd = (unsigned)sm[(size_t)row_of_code[c] * W + j];
+                const unsigned rc_ = (unsigned)sm[(size_t)row_of_code[c ^ 2] * W + (W - 1 - j)];   // comp: A <-> T, C <-> G
+                ftab[(size_t)j * 8 + c] = fwd | (rc_ << 16);
+            }
+    }
+    const size_t o_ftab = carve(ftab.size() * sizeof(unsigned));
+    const size_t o_pmf = carve(sizeof(double) * (size_t)m->L);
+    const size_t o_ptable = carve(sizeof(double) * (size_t)m->L);
+    const size_t o_dp = carve(sizeof(double) * 2 * (size_t)m->L);
+    const size_t o_qwork = carve(sizeof(QWork) * kQStreams);
+    const size_t o_qscratch = carve(sizeof(double) * (size_t)m->L * kQStreams);
+    size_t o_partials[kWorkspaces], o_resid[kWorkspaces], o_resid_n[kWorkspaces], o_spill[kWorkspaces];
+    for (int i = 0; i < kWorkspaces; ++i) {
+        o_partials[i] = carve(sizeof(unsigned) * (size_t)m->max_slabs * (size_t)(m->part_nb + 1));
+        o_resid[i] = carve(sizeof(long long) * (size_t)m->max_slabs * kResidPerWG);
+        o_resid_n[i] = carve(sizeof(int) * (size_t)m->max_slabs);
+    }
+    const size_t o_sel_resid = carve(sizeof(long long) * (size_t)m->sel_slabs * kResidPerWG);
+    const size_t o_sel_resid_n = carve(sizeof(int) * (size_t)m->sel_slabs);
+    const size_t o_zero = slab_bytes;                 // what follows starts out zeroed
+    for (int i = 0; i < kWorkspaces; ++i) o_spill[i] = carve(sizeof(unsigned) * (size_t)m->nb * (size_t)kSpillCopies);
+    const size_t o_ctl = carve(sizeof(HitCtl));
+    const size_t o_sel_ctl = carve(sizeof(HitCtl));
+    HIP_TRY(hipMalloc(&m->d_slab, slab_bytes));
+    HIP_TRY(hipMemsetAsync(m->d_slab + o_zero, 0, slab_bytes - o_zero, nullptr));
+    m->d_tab = reinterpret_cast<uint16_t *>(m->d_slab + o_tab);
+    m->d_ftab = reinterpret_cast<unsigned *>(m->d_slab + o_ftab);
+    m->d_pmf = reinterpret_cast<double *>(m->d_slab + o_pmf);
+    m->d_ptable = reinterpret_cast<double *>(m->d_slab + o_ptable);
+    m->d_qwork = reinterpret_cast<QWork *>(m->d_slab + o_qwork);
+    m->d_qscratch = reinterpret_cast<double *>(m->d_slab + o_qscratch);
+    for (int i = 0; i < kWorkspaces; ++i) {
+        m->d_partials[i] = reinterpret_cast<unsigned *>(m->d_slab + o_partials[i]);
+        m->d_resid[i] = reinterpret_cast<long long *>(m->d_slab + o_resid[i]);
+        m->d_resid_n[i] = reinterpret_cast<int *>(m->d_slab + o_resid_n[i]);
+        m->d_spill[i] = reinterpret_cast<unsigned *>(m->d_slab + o_spill[i]);
+        HIP_TRY(hipEventCreateWithFlags(&m->ev_scored[i], hipEventDisableTiming | hipEventReleaseToDevice));
+        HIP_TRY(hipEventCreateWithFlags(&m->ev_posted[i], hipEventDisableTiming | hipEventReleaseToDevice));
+    }
+    HIP_TRY(hipEventCreateWithFlags(&m->ev_selected, hipEventDisableTiming));
+    m->d_sel_resid = reinterpret_cast<long long *>(m->d_slab + o_sel_resid);
+    m->d_sel_resid_n = reinterpret_cast<int *>(m->d_slab + o_sel_resid_n);
+    m->d_ctl = reinterpret_cast<HitCtl *>(m->d_slab + o_ctl);
+    m->d_sel_ctl = reinterpret_cast<HitCtl *>(m->d_slab + o_sel_ctl);
+    *d_rows = reinterpret_cast<double *>(m->d_slab + o_dp);
+
+    HIP_TRY(hipMemcpyAsync(m->d_tab, tab.data(), tab.size() * sizeof(uint16_t), hipMemcpyHostToDevice, nullptr));
+    HIP_TRY(hipMemcpyAsync(m->d_ftab, ftab.data(), ftab.size() * sizeof(unsigned), hipMemcpyHostToDevice, nullptr));
+    return GFM_OK;
+}
+
+// The decisions of a handle that read its tail table (h_ptable): waves per workgroup and histogram window of the
+// single-motif launch, then the LDS limit of every score-kernel instantiation its width can use
+int motif_finish(gfm_motif *m)
+{
+    const int W = m->W;
+    long long room16, room8;
+    score_rooms(W, &room16, &room8);
+    constexpr double kWindowMass16 = 0.9999;   // a partial window beside 16 waves must hold this much
+    m->q_waves = kWavesPerWG;
+    if (m->nb <= room16) {
+        m->hnb = m->nb;
+    } else if (room16 >= 256 && best_window(m, (int)room16).mass >= kWindowMass16) {
+        m->hnb = (int)room16;
+    } else {
+        m->q_waves = kWavesPerWG / 2;
+        m->hnb = (int)std::min<long long>(m->nb, room8);
+    }
+#ifdef GFM_LAB
+    if (const char *e = std::getenv("GRAFIMO_SCORE_WAVES")) {   // force 8 or 16 waves
+        const int wv = atoi(e);
+        if (wv == 8 || (wv == 16 && room16 >= 256)) {
+            m->q_waves = wv;
+            m->hnb = (int)std::min<long long>(m->nb, wv == 8 ? room8 : room16);
+        }
+    }
+#endif
+    m->hlo = best_window(m, m->hnb).lo;   // partial when the range does not fit: the rest spills
+    m->lds_bytes = quad_fixed_lds(W, m->q_waves) + sizeof(unsigned) * (size_t)(m->hnb + 1);
+    // allow up to the whole LDS for every instantiation this width can use
+    ScoreArgs<3> none{};
+    int rc = GFM_OK;
+    for (int mm = 1; mm <= (W <= kQuadMaxBatchWidth ? 3 : 1) && !rc; ++mm)
+        rc = dispatch_quad(W, mm, nullptr, nullptr, 0, 0, &none, 0, 1, m->q_waves, nullptr, true);
+    return rc;
+}
+
+}  // namespace
+
+// One device pass for a motif set: all checks first, then one upload, ONE launch of the DP (one workgroup per motif),
+// one copy back.  Motif i's score matrix starts at sum_{j<i} 4 W_j, its distribution at sum_{j<i} (1000 W_j + 1).
+GFM_API int gfm_comp_pval_mat_many(int n_motifs, const int64_t *h_score_matrices, const int *widths, const double *h_bgs,
+                                   double *h_pmf_out)
+{
+    if (n_motifs < 0) return fail(GFM_ERR_INVALID, "negative motif count %d", n_motifs);
+    if (n_motifs == 0) return GFM_OK;
+    if (!h_score_matrices || !widths || !h_bgs || !h_pmf_out) return fail(GFM_ERR_INVALID, "NULL argument");
+    size_t at = 0, total_L = 0;
+    for (int i = 0; i < n_motifs; ++i) {
+        const int rc = validate_motif(i, h_score_matrices + at, widths[i], h_bgs + 4 * (size_t)i, nullptr, nullptr);
+        if (rc) return rc;
+        at += 4 * (size_t)widths[i];
+        total_L += (size_t)kRange * widths[i] + 1;
+    }
+    int rc = ensure_device();
+    if (rc) return rc;
+    DpPack pk;
+    at = 0;
+    for (int i = 0; i < n_motifs; ++i) {
+        pk.add(h_score_matrices + at, widths[i], h_bgs + 4 * (size_t)i);
+        at += 4 * (size_t)widths[i];
+    }
+    // [pack | rows: 2 L per motif | distributions: L per motif, laid out as h_pmf_out]
+    const size_t rows_at = align256(pk.bytes()), pmf_at = rows_at + align256(sizeof(double) * 2 * total_L);
+    std::vector<unsigned char> img;   // (declared before the device buffer: on an error return the buffer's free,
+    DevBuf<unsigned char> d;          //  which waits for the device, comes first)
+    HIP_TRY(d.alloc(pmf_at + sizeof(double) * total_L));
+    double *rows = reinterpret_cast<double *>(d.p + rows_at), *pmfs = reinterpret_cast<double *>(d.p + pmf_at);
+    size_t off = 0;
+    for (DpJob &j : pk.jobs) {
+        j.buf = rows + 2 * off;
+        j.pmf = pmfs + off;
+        off += (size_t)j.L;
+    }
+    img = pk.image();
+    HIP_TRY(hipMemcpyAsync(d.p, img.data(), img.size(), hipMemcpyHostToDevice, nullptr));
+    rc = pk.launch(d.p, n_motifs, false, nullptr);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpy(h_pmf_out, pmfs, sizeof(double) * total_L, hipMemcpyDeviceToHost));
+    return GFM_OK;
+}
+
 GFM_API int gfm_comp_pval_mat(const int64_t *sm, int W, const double *bg, double *h_pmf)
 {
-    if (!bg || !h_pmf) return fail(GFM_ERR_INVALID, "NULL argument");
-    int rc = validate_matrix(sm, W);
-    if (rc) return rc;
-    for (int n = 0; n < 4; ++n)
-        if (!(bg[n] > 0)) return fail(GFM_ERR_ASSERT, "assert bg > 0 (motif_processing.pyx:592)");
-    rc = ensure_device();
-    if (rc) return rc;
-    const int L = kRange * W + 1;
-    DevBuf<double> d_pmf;
-    HIP_TRY(d_pmf.alloc((size_t)L));
-    rc = run_dp(sm, W, bg, d_pmf, nullptr);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpy(h_pmf, d_pmf, sizeof(double) * (size_t)L, hipMemcpyDeviceToHost));
-    return GFM_OK;
+    return gfm_comp_pval_mat_many(1, sm, &W, bg, h_pmf);
 }
 
 GFM_API void gfm_motif_destroy(gfm_motif_t m)
@@ -547,197 +795,98 @@ GFM_API void gfm_motif_destroy(gfm_motif_t m)
     delete m;
 }
 
-GFM_API int gfm_motif_create(const int64_t *sm, int W, const double *bg, int min_val, int scale,
-                             double offset, const double *h_pmf, gfm_motif_t *out)
+// M handles in one device pass: every check first; then the host tables and one slab per handle (the LRU cache of
+// device.py destroys handles one at a time), one packed upload, ONE DP launch for the motifs without a given
+// distribution, ONE tail-table launch for all of them, one synchronisation, and the per-handle choices that read the
+// tail table.  All or nothing: on failure every out[i] is NULL and nothing is left allocated.
+GFM_API int gfm_motif_create_many(int n_motifs, const int64_t *h_score_matrices, const int *widths, const double *h_bgs,
+                                  const int *min_vals, const int *scales, const double *offsets,
+                                  const double *const *h_pmfs, gfm_motif_t *out)
 {
-    if (!out || !bg) return fail(GFM_ERR_INVALID, "NULL argument");
-    *out = nullptr;
-    int rc = validate_matrix(sm, W);
-    if (rc) return rc;
-    if (scale <= 0) return fail(GFM_ERR_INVALID, "scale must be a positive integer");
-    {   // min_val indexes the histogram and the tables on the device: it must be the matrix minimum
-        // (Motif.min_val, motif_ops.py:1106), the score of a k-mer holding N (score_sequences.py:376-378)
-        int64_t mn = sm[0];
-        for (int i = 1; i < 4 * W; ++i) mn = std::min(mn, sm[i]);
-        if ((int64_t)min_val != mn)
-            return fail(GFM_ERR_INVALID, "min_val %d is not the minimum of the score matrix (%lld)", min_val, (long long)mn);
+    if (n_motifs < 0) return fail(GFM_ERR_INVALID, "negative motif count %d", n_motifs);
+    if (!out) return fail(GFM_ERR_INVALID, "NULL argument");
+    for (int i = 0; i < n_motifs; ++i) out[i] = nullptr;
+    if (n_motifs == 0) return GFM_OK;
+    if (!h_score_matrices || !widths || !h_bgs || !min_vals || !scales || !offsets)
+        return fail(GFM_ERR_INVALID, "NULL argument");
+    std::vector<size_t> sm_at((size_t)n_motifs);
+    size_t at = 0;
+    for (int i = 0; i < n_motifs; ++i) {
+        sm_at[(size_t)i] = at;
+        const int rc = validate_motif(i, h_score_matrices + at, widths[i], h_bgs + 4 * (size_t)i, &min_vals[i], &scales[i]);
+        if (rc) return rc;
+        at += 4 * (size_t)widths[i];
     }
-    for (int n = 0; n < 4; ++n)
-        if (!(bg[n] > 0)) return fail(GFM_ERR_ASSERT, "assert bg > 0");
-    rc = ensure_device();
+    int rc = ensure_device();
     if (rc) return rc;
 
-    gfm_motif *m = new (std::nothrow) gfm_motif();
-    if (!m) return fail(GFM_ERR_NOMEM, "out of host memory");
-    m->W = W;
-    m->L = kRange * W + 1;
-    m->min_val = min_val;
-    m->scale = scale;
-    m->offset = offset;
-    m->ndw = (W + 3) / 4;
-    m->sm.assign(sm, sm + 4 * W);
-    std::memcpy(m->bg, bg, sizeof m->bg);
-    std::vector<int> clo, chi;
-    cumulative_windows(sm, W, clo, chi);
-    m->lo = clo[W - 1];
-    m->hi = chi[W - 1];
-    m->nb = m->hi - m->lo + 1;
-
-    auto bail = [&](int code) { gfm_motif_destroy(m); return code; };
-#define HIP_TRY_M(expr)                                                                      \
+    // host data the asynchronous copies read: declared before the handles and the device buffer, so that it outlives them
+    std::vector<std::vector<uint16_t>> tabs((size_t)n_motifs);
+    std::vector<std::vector<unsigned>> ftabs((size_t)n_motifs);
+    std::vector<unsigned char> img;
+    DevBuf<unsigned char> d_pack;
+    std::vector<gfm_motif *> ms((size_t)n_motifs, nullptr);
+    auto bail = [&](int code) {
+        (void)hipStreamSynchronize(nullptr);   // nothing enqueued may still read or write what is freed here
+        for (gfm_motif *m : ms) gfm_motif_destroy(m);
+        return code;
+    };
+#define HIP_TRY_B(expr)                                                                      \
     do {                                                                                     \
         hipError_t e_ = (expr);                                                              \
         if (e_ != hipSuccess)                                                                \
             return bail(fail(GFM_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)));   \
     } while (0)
 
-    HIP_TRY_M(hipGetDevice(&m->device));
-    {   // compute-unit count of the device, queried once per process (hipGetDeviceProperties is slow)
-        static std::atomic<int> cu_of[64];
-        int cu = cu_of[m->device & 63].load(std::memory_order_acquire);
-        if (cu == 0) {
-            HIP_TRY_M(hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, m->device));
-            if (cu <= 0) cu = 256;
-            cu_of[m->device & 63].store(cu, std::memory_order_release);
-        }
-        m->n_cu = cu;
-    }
-    if (const char *e = std::getenv("GRAFIMO_RESERVE_CUS")) m->reserve_cus = std::max(0, std::min(atoi(e), m->n_cu - 1));
-
-    // LDS lookup tables: [2*ndw base pairs][8 x 8 codes] uint16, code = (ascii >> 1) & 7
-    // (A 0, C 1, T 2, G 3; 4..7 invalid), index = code(first) + 8 * code(second).
-    // A valid pair holds sm[first][2p] + sm[second][2p+1]; a pair with an invalid code holds
-    // kPoison; a position >= W contributes 0 and accepts any code.
-    std::vector<uint16_t> tab((size_t)2 * m->ndw * 64, 0);
-    auto base_score = [&](int pos, int code, bool *bad) -> unsigned {
-        if (pos >= W) return 0u;
-        static const int nuc_of_code[4] = {0, 1, 3, 2};  // code 2 = T (row 3), code 3 = G (row 2)
-        if (code > 3) { *bad = true; return 0u; }
-        return (unsigned)sm[nuc_of_code[code] * W + pos];
-    };
-    for (int pr = 0; pr < 2 * m->ndw; ++pr)
-        for (int c1 = 0; c1 < 8; ++c1)
-            for (int c0 = 0; c0 < 8; ++c0) {
-                bool bad = false;
-                const unsigned v = base_score(2 * pr, c0, &bad) + base_score(2 * pr + 1, c1, &bad);
-                tab[(size_t)pr * 64 + c0 + 8 * c1] = (uint16_t)(bad ? kPoison : v);
-            }
-    // score-kernel LDS plan: pair tables | wave strips + hit queues | histogram window (+1 N bin).  With 16 waves
-    // the strips leave room16 bins; a reachable range that does not fit gets the whole LDS of an 8-wave
-    // workgroup (half the strips) unless a 16-wave window still covers practically all of the background
-    // mass (decided below, once the tail table exists).
-    const long long room16 = ((long long)kMaxLdsBytes - (long long)quad_fixed_lds(W, kWavesPerWG)) / (long long)sizeof(unsigned) - 1;
-    const long long room8 = ((long long)kMaxLdsBytes - (long long)quad_fixed_lds(W, kWavesPerWG / 2)) / (long long)sizeof(unsigned) - 1;
-    if (room8 < 256) return bail(fail(GFM_ERR_INVALID, "no LDS left for a histogram window at width %d", W));
-    // (batched launches carry bigger tables and more hit queues: their windows are never larger than these)
-    m->part_nb = (int)std::min<long long>(m->nb, std::max(room16, room8));
-    m->max_slabs = m->n_cu * kWGsPerCU;
-    m->sel_slabs = 4 * m->n_cu;
-
-    // ONE device allocation for the motif (a motif set creates hundreds of these; ~20 hipMalloc /
-    // hipFree pairs per motif were most of the creation time)
-    size_t slab_bytes = 0;
-    auto carve = [&](size_t bytes) { const size_t at = slab_bytes; slab_bytes += (bytes + 255) & ~(size_t)255; return at; };
-    const size_t o_tab = carve(tab.size() * sizeof(uint16_t));
-    // the fused extraction -> scoring kernels' table (gfm_graph_fused.hpp): ONE lookup per base serves both strands -- the
-    // reverse complement holds comp(base j) at position W-1-j; code 2 = T (row 3), code 3 = G (row 2); codes 4..7 hold 0
-    std::vector<unsigned> ftab((size_t)W * 8, 0u);
-    {
-        static const int row_of_code[4] = {0, 1, 3, 2};
-        for (int j = 0; j < W; ++j)
-            for (int c = 0; c < 4; ++c) {
-                const unsigned fwd = (unsigned)sm[(size_t)row_of_code[c] * W + j];
-                const unsigned rc_ = (unsigned)sm[(size_t)row_of_code[c ^ 2] * W + (W - 1 - j)];   // comp: A <-> T, C <-> G
-                ftab[(size_t)j * 8 + c] = fwd | (rc_ << 16);
-            }
-    }
-    const size_t o_ftab = carve(ftab.size() * sizeof(unsigned));
-    const size_t o_pmf = carve(sizeof(double) * (size_t)m->L);
-    const size_t o_ptable = carve(sizeof(double) * (size_t)m->L);
-    const size_t o_dp = carve(dp_scratch_bytes(W));
-    const size_t o_qwork = carve(sizeof(QWork) * kQStreams);
-    const size_t o_qscratch = carve(sizeof(double) * (size_t)m->L * kQStreams);
-    size_t o_partials[kWorkspaces], o_resid[kWorkspaces], o_resid_n[kWorkspaces], o_spill[kWorkspaces];
-    for (int i = 0; i < kWorkspaces; ++i) {
-        o_partials[i] = carve(sizeof(unsigned) * (size_t)m->max_slabs * (size_t)(m->part_nb + 1));
-        o_resid[i] = carve(sizeof(long long) * (size_t)m->max_slabs * kResidPerWG);
-        o_resid_n[i] = carve(sizeof(int) * (size_t)m->max_slabs);
-    }
-    const size_t o_sel_resid = carve(sizeof(long long) * (size_t)m->sel_slabs * kResidPerWG);
-    const size_t o_sel_resid_n = carve(sizeof(int) * (size_t)m->sel_slabs);
-    const size_t o_zero = slab_bytes;                 // what follows starts out zeroed
-    for (int i = 0; i < kWorkspaces; ++i) o_spill[i] = carve(sizeof(unsigned) * (size_t)m->nb * (size_t)kSpillCopies);
-    const size_t o_ctl = carve(sizeof(HitCtl));
-    const size_t o_sel_ctl = carve(sizeof(HitCtl));
-    HIP_TRY_M(hipMalloc(&m->d_slab, slab_bytes));
-    HIP_TRY_M(hipMemsetAsync(m->d_slab + o_zero, 0, slab_bytes - o_zero, nullptr));
-    m->d_tab = reinterpret_cast<uint16_t *>(m->d_slab + o_tab);
-    m->d_ftab = reinterpret_cast<unsigned *>(m->d_slab + o_ftab);
-    m->d_pmf = reinterpret_cast<double *>(m->d_slab + o_pmf);
-    m->d_ptable = reinterpret_cast<double *>(m->d_slab + o_ptable);
-    m->d_qwork = reinterpret_cast<QWork *>(m->d_slab + o_qwork);
-    m->d_qscratch = reinterpret_cast<double *>(m->d_slab + o_qscratch);
-    for (int i = 0; i < kWorkspaces; ++i) {
-        m->d_partials[i] = reinterpret_cast<unsigned *>(m->d_slab + o_partials[i]);
-        m->d_resid[i] = reinterpret_cast<long long *>(m->d_slab + o_resid[i]);
-        m->d_resid_n[i] = reinterpret_cast<int *>(m->d_slab + o_resid_n[i]);
-        m->d_spill[i] = reinterpret_cast<unsigned *>(m->d_slab + o_spill[i]);
-        HIP_TRY_M(hipEventCreateWithFlags(&m->ev_scored[i], hipEventDisableTiming | hipEventReleaseToDevice));
-        HIP_TRY_M(hipEventCreateWithFlags(&m->ev_posted[i], hipEventDisableTiming | hipEventReleaseToDevice));
-    }
-    HIP_TRY_M(hipEventCreateWithFlags(&m->ev_selected, hipEventDisableTiming));
-    m->d_sel_resid = reinterpret_cast<long long *>(m->d_slab + o_sel_resid);
-    m->d_sel_resid_n = reinterpret_cast<int *>(m->d_slab + o_sel_resid_n);
-    m->d_ctl = reinterpret_cast<HitCtl *>(m->d_slab + o_ctl);
-    m->d_sel_ctl = reinterpret_cast<HitCtl *>(m->d_slab + o_sel_ctl);
-
-    HIP_TRY_M(hipMemcpyAsync(m->d_tab, tab.data(), tab.size() * sizeof(uint16_t), hipMemcpyHostToDevice, nullptr));
-    HIP_TRY_M(hipMemcpyAsync(m->d_ftab, ftab.data(), ftab.size() * sizeof(unsigned), hipMemcpyHostToDevice, nullptr));
-    if (h_pmf) {
-        HIP_TRY_M(hipMemcpyAsync(m->d_pmf, h_pmf, sizeof(double) * (size_t)m->L, hipMemcpyHostToDevice, nullptr));
-    } else {
-        rc = run_dp(sm, W, bg, m->d_pmf, nullptr, m->d_slab + o_dp);
+    std::vector<double *> rows((size_t)n_motifs, nullptr);
+    for (int i = 0; i < n_motifs; ++i) {
+        gfm_motif *m = ms[(size_t)i] = new (std::nothrow) gfm_motif();
+        if (!m) return bail(fail(GFM_ERR_NOMEM, "out of host memory"));
+        rc = motif_alloc(m, h_score_matrices + sm_at[(size_t)i], widths[i], h_bgs + 4 * (size_t)i, min_vals[i], scales[i],
+                         offsets[i], tabs[(size_t)i], ftabs[(size_t)i], &rows[(size_t)i]);
         if (rc) return bail(rc);
     }
-    hipLaunchKernelGGL(ptable_kernel, dim3(1), dim3(kScanThreads), 0, nullptr, m->d_pmf, m->L,
-                       m->lo, m->hi, m->d_ptable);
-    HIP_TRY_M(hipGetLastError());
-    m->h_ptable.resize(m->L);
-    HIP_TRY_M(hipMemcpy(m->h_ptable.data(), m->d_ptable, sizeof(double) * (size_t)m->L,
-                        hipMemcpyDeviceToHost));       // also completes the async copies of `tab` / h_pmf
-    {   // waves per workgroup and histogram window of the single-motif launch
-        constexpr double kWindowMass16 = 0.9999;   // a partial window beside 16 waves must hold this much
-        m->q_waves = kWavesPerWG;
-        if (m->nb <= room16) {
-            m->hnb = m->nb;
-        } else if (room16 >= 256 && best_window(m, (int)room16).mass >= kWindowMass16) {
-            m->hnb = (int)room16;
-        } else {
-            m->q_waves = kWavesPerWG / 2;
-            m->hnb = (int)std::min<long long>(m->nb, room8);
+    // the motifs that need the DP first: the DP launch serves jobs [0, n_dp), the tail-table launch all of them
+    DpPack pk;
+    int n_dp = 0;
+    for (int pass = 0; pass < 2; ++pass)
+        for (int i = 0; i < n_motifs; ++i) {
+            const double *given = h_pmfs ? h_pmfs[i] : nullptr;
+            if ((given != nullptr) != (pass == 1)) continue;
+            gfm_motif *m = ms[(size_t)i];
+            DpJob &j = pk.add(h_score_matrices + sm_at[(size_t)i], widths[i], h_bgs + 4 * (size_t)i);
+            j.buf = rows[(size_t)i];
+            j.pmf = m->d_pmf;
+            j.ptable = m->d_ptable;
+            if (given)
+                HIP_TRY_B(hipMemcpyAsync(m->d_pmf, given, sizeof(double) * (size_t)m->L, hipMemcpyHostToDevice, nullptr));
+            else
+                ++n_dp;
         }
-#ifdef GFM_LAB
-        if (const char *e = std::getenv("GRAFIMO_SCORE_WAVES")) {   // force 8 or 16 waves
-            const int wv = atoi(e);
-            if (wv == 8 || (wv == 16 && room16 >= 256)) {
-                m->q_waves = wv;
-                m->hnb = (int)std::min<long long>(m->nb, wv == 8 ? room8 : room16);
-            }
-        }
-#endif
-        m->hlo = best_window(m, m->hnb).lo;   // partial when the range does not fit: the rest spills
-        m->lds_bytes = quad_fixed_lds(W, m->q_waves) + sizeof(unsigned) * (size_t)(m->hnb + 1);
+    img = pk.image();
+    HIP_TRY_B(d_pack.alloc(img.size()));
+    HIP_TRY_B(hipMemcpyAsync(d_pack.p, img.data(), img.size(), hipMemcpyHostToDevice, nullptr));
+    rc = pk.launch(d_pack.p, n_dp, true, nullptr);
+    if (rc) return bail(rc);
+    for (gfm_motif *m : ms) {
+        m->h_ptable.resize((size_t)m->L);
+        HIP_TRY_B(hipMemcpyAsync(m->h_ptable.data(), m->d_ptable, sizeof(double) * (size_t)m->L, hipMemcpyDeviceToHost,
+                                 nullptr));
     }
-#undef HIP_TRY_M
-    {   // allow up to the whole LDS for every instantiation this width can use
-        ScoreArgs<3> none{};
-        rc = GFM_OK;
-        for (int mm = 1; mm <= (W <= kQuadMaxBatchWidth ? 3 : 1) && !rc; ++mm)
-            rc = dispatch_quad(W, mm, nullptr, nullptr, 0, 0, &none, 0, 1, m->q_waves, nullptr, true);
+    HIP_TRY_B(hipStreamSynchronize(nullptr));   // the one wait: uploads, both launches and the tail tables' copies
+#undef HIP_TRY_B
+    for (gfm_motif *m : ms) {
+        rc = motif_finish(m);
         if (rc) return bail(rc);
     }
-    *out = m;
+    for (int i = 0; i < n_motifs; ++i) out[i] = ms[(size_t)i];
     return GFM_OK;
+}
+
+GFM_API int gfm_motif_create(const int64_t *sm, int W, const double *bg, int min_val, int scale,
+                             double offset, const double *h_pmf, gfm_motif_t *out)
+{
+    return gfm_motif_create_many(1, sm, &W, bg, &min_val, &scale, &offset, &h_pmf, out);
 }
 
 GFM_API int gfm_motif_width(gfm_motif_t m) { return m ? m->W : 0; }

@@ -5,7 +5,7 @@ buffers, streams and (in distributed.py) torch.distributed over RCCL.
 """
 import ctypes
 from collections import OrderedDict
-from typing import Optional
+from typing import List, Optional
 
 import numpy as np
 
@@ -48,6 +48,14 @@ class DeviceMotif:
     """
 
     def __init__(self, score_matrix, bg, min_val, scale, offset, pmf: Optional[np.ndarray] = None):
+        sm, bg, pmf = self._set_numbers(score_matrix, bg, min_val, scale, offset, pmf)
+        h = ctypes.c_void_p()
+        nv.check(nv.lib().gfm_motif_create(nv.ptr(sm), self.width, nv.ptr(bg), self.min_val,
+                                           self.scale, self.offset, nv.ptr(pmf), ctypes.byref(h)))
+        self._adopt(h)
+
+    def _set_numbers(self, score_matrix, bg, min_val, scale, offset, pmf):
+        """The scalar members; -> (score matrix int64 [4, W], bg f64, pmf f64 [L] or None) as the library reads them."""
         sm = np.ascontiguousarray(score_matrix, dtype=np.int64)
         if sm.ndim != 2 or sm.shape[0] != 4:
             raise ValueError("score_matrix must be [4, W]")
@@ -61,25 +69,55 @@ class DeviceMotif:
             pmf = np.ascontiguousarray(pmf, dtype=np.float64)
             if pmf.shape != (self.L,):
                 raise ValueError(f"pval_matrix must have {self.L} entries")
-        h = ctypes.c_void_p()
-        nv.check(nv.lib().gfm_motif_create(nv.ptr(sm), self.width, nv.ptr(bg), self.min_val,
-                                           self.scale, self.offset, nv.ptr(pmf), ctypes.byref(h)))
+        return sm, bg, pmf
+
+    def _adopt(self, h):
         self._h = h
         lo, hi = ctypes.c_int32(), ctypes.c_int32()
         nv.check(nv.lib().gfm_motif_score_range(self._h, ctypes.byref(lo), ctypes.byref(hi)))
         self.score_lo, self.score_hi = lo.value, hi.value
 
+    @staticmethod
+    def _numbers_of(motif, use_motif_pmf=True):
+        """(score matrix, bg, min_val, scale, offset, pmf or None) of a Motif: what a handle is made of."""
+        from .motif import dense_bg, dense_score_matrix
+        pmf = getattr(motif, "pval_matrix", None) if use_motif_pmf else None   # not computed yet: the DP runs on the device
+        return (dense_score_matrix(motif), dense_bg(motif), int(motif.min_val), int(motif.scale), float(motif.offset), pmf)
+
     @classmethod
     def from_motif(cls, motif, use_motif_pmf=True):
-        pmf = None
-        if use_motif_pmf:
-            try:
-                pmf = motif.pval_matrix
-            except AttributeError:     # not computed yet: the DP runs on the device
-                pmf = None
-        from .motif import dense_bg, dense_score_matrix
-        return cls(dense_score_matrix(motif), dense_bg(motif), int(motif.min_val), int(motif.scale),
-                   float(motif.offset), pmf)
+        return cls(*cls._numbers_of(motif, use_motif_pmf))
+
+    @classmethod
+    def create_many(cls, motifs, use_motif_pmf=True) -> List["DeviceMotif"]:
+        """Handles for a motif set in ONE gfm_motif_create_many call: one DP launch for the motifs without a pval_matrix
+        (or all of them, use_motif_pmf=False), one tail-table launch, one synchronisation.  Each handle equals
+        from_motif(motif) and is closed on its own.  All or nothing: on an error no handle is left."""
+        return cls._create_many([cls._numbers_of(m, use_motif_pmf) for m in motifs])
+
+    @classmethod
+    def _create_many(cls, specs) -> List["DeviceMotif"]:
+        """specs: (score matrix, bg, min_val, scale, offset, pmf or None) per handle."""
+        M = len(specs)
+        if M == 0:
+            return []
+        dms = [cls.__new__(cls) for _ in range(M)]
+        arrays = [dm._set_numbers(*spec) for dm, spec in zip(dms, specs)]
+        if any(bg.shape != (4,) for _, bg, _ in arrays):
+            raise ValueError("bg must hold 4 probabilities")
+        sm_all = np.concatenate([sm.ravel() for sm, _, _ in arrays])
+        widths = np.array([dm.width for dm in dms], dtype=np.int32)
+        bgs = np.ascontiguousarray(np.stack([bg for _, bg, _ in arrays]))
+        min_vals = np.array([dm.min_val for dm in dms], dtype=np.int32)
+        scales = np.array([dm.scale for dm in dms], dtype=np.int32)
+        offsets = np.array([dm.offset for dm in dms], dtype=np.float64)
+        pmfs = (ctypes.c_void_p * M)(*[nv.ptr(pmf) for _, _, pmf in arrays])
+        hs = (ctypes.c_void_p * M)()
+        nv.check(nv.lib().gfm_motif_create_many(M, nv.ptr(sm_all), nv.ptr(widths), nv.ptr(bgs), nv.ptr(min_vals),
+                                                nv.ptr(scales), nv.ptr(offsets), pmfs, hs))
+        for dm, h in zip(dms, hs):
+            dm._adopt(ctypes.c_void_p(h))
+        return dms
 
     def close(self):
         if getattr(self, "_h", None):
@@ -97,26 +135,76 @@ class DeviceMotif:
     _KEEP = max(1, int(__import__("os").environ.get("GRAFIMO_MOTIF_CACHE", 64)))
 
     @classmethod
+    def _lease_key_of(cls, spec):
+        sm, bg, min_val, scale, offset, pmf = spec
+        return (_torch().cuda.current_device(), np.ascontiguousarray(sm, dtype=np.int64).tobytes(),
+                np.ascontiguousarray(bg, dtype=np.float64).tobytes(), min_val, scale, offset,
+                None if pmf is None else _fingerprint(pmf))
+
+    @classmethod
+    def _evict_for(cls, n_new):
+        """Destroy kept handles nobody holds, least recently used first, until n_new more fit under _KEEP."""
+        for old in [k for k, v in cls._kept.items() if v[1] == 0][:max(0, len(cls._kept) + n_new - cls._KEEP)]:
+            cls._kept.pop(old)[0].close()
+
+    @classmethod
     def lease(cls, motif, use_motif_pmf=True) -> "DeviceMotif":
         """A handle for `motif` on the current device, a kept one if the same numbers were leased before.  Give it
         back with `release()`, not `close()`."""
-        from .motif import dense_bg, dense_score_matrix
-        pmf = getattr(motif, "pval_matrix", None) if use_motif_pmf else None
-        sm, bg = dense_score_matrix(motif), dense_bg(motif)
-        key = (_torch().cuda.current_device(), np.ascontiguousarray(sm, dtype=np.int64).tobytes(),
-               np.ascontiguousarray(bg, dtype=np.float64).tobytes(), int(motif.min_val), int(motif.scale), float(motif.offset),
-               None if pmf is None else _fingerprint(pmf))
+        spec = cls._numbers_of(motif, use_motif_pmf)
+        key = cls._lease_key_of(spec)
         slot = cls._kept.get(key)
         if slot is not None and slot[0]._h:
             slot[1] += 1
             cls._kept.move_to_end(key)
             return slot[0]
-        dm = cls(sm, bg, int(motif.min_val), int(motif.scale), float(motif.offset), pmf)
+        dm = cls(*spec)
         dm._lease_key = key
         cls._kept[key] = [dm, 1]
-        for old in [k for k, v in cls._kept.items() if v[1] == 0][:max(0, len(cls._kept) - cls._KEEP)]:
-            cls._kept.pop(old)[0].close()
+        cls._evict_for(0)
         return dm
+
+    @classmethod
+    def lease_many(cls, motifs, use_motif_pmf=True, distinct=False) -> List["DeviceMotif"]:
+        """lease() for a motif set: kept handles are reused, the misses are created in ONE create_many call (one DP and
+        one tail-table launch).  The same numbers twice in the set share one handle, or with distinct=True the later
+        ones get a handle of their own that is not kept (a handle's workspace holds ONE histogram).  Give each back with
+        release().  The handles nobody holds are evicted as by lease(), before the new ones are allocated."""
+        specs = [cls._numbers_of(m, use_motif_pmf) for m in motifs]
+        keys = [cls._lease_key_of(spec) for spec in specs]
+        out: List[Optional[DeviceMotif]] = [None] * len(motifs)
+        first = {}                 # key -> index of its first occurrence in the set
+        make, shared, leased = [], [], []
+        for i, key in enumerate(keys):
+            if key in first:       # the same numbers again
+                (make if distinct else shared).append(i)
+                continue
+            first[key] = i
+            slot = cls._kept.get(key)
+            if slot is not None and slot[0]._h:
+                slot[1] += 1
+                cls._kept.move_to_end(key)
+                out[i] = slot[0]
+                leased.append(slot[0])
+            else:
+                make.append(i)
+        try:
+            cls._evict_for(sum(1 for i in make if first[keys[i]] == i and keys[i] not in cls._kept))
+            made = cls._create_many([specs[i] for i in make])
+        except BaseException:
+            for dm in leased:
+                dm.release()
+            raise
+        for i, dm in zip(make, made):
+            out[i] = dm
+            if first[keys[i]] == i:            # kept; a distinct copy of a number seen before is not
+                dm._lease_key = keys[i]
+                cls._kept[keys[i]] = [dm, 1]
+        for i in shared:
+            slot = cls._kept[keys[i]]
+            slot[1] += 1
+            out[i] = slot[0]
+        return out
 
     def release(self):
         slot = DeviceMotif._kept.get(getattr(self, "_lease_key", None))

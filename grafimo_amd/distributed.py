@@ -134,7 +134,7 @@ class HipBackend(ScanBackend):
         from .device import DeviceMotif
         from .score_sequences import StreamScan
         dev = torch.device("cuda", torch.cuda.current_device())
-        dms = [DeviceMotif.from_motif(m) for m in motifs]
+        dms = DeviceMotif.create_many(motifs)     # one device pass for the shard's handles
 
         class HipShardScan:
             device = dev

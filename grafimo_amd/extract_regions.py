@@ -1790,13 +1790,9 @@ class _FusedPass:
         self.got = None
         self.cols = None
         self._run = None
-        self.dms = []
-        for m in motifs:                 # kept handles when these motifs were scored before (device.py); the same numbers twice in
-            dm = DeviceMotif.lease(m)    # one set: a handle of its own (a handle's workspace holds ONE histogram)
-            if any(dm is d for d in self.dms):
-                dm.release()
-                dm = DeviceMotif.from_motif(m)
-            self.dms.append(dm)
+        # kept handles when these motifs were scored before (device.py), the others made in one pass; the same numbers twice in
+        # one set: a handle of its own (a handle's workspace holds ONE histogram)
+        self.dms = DeviceMotif.lease_many(self.motifs, distinct=True)
         try:
             M = len(self.dms)
             self.L = self.dms[0].L

@@ -29,7 +29,8 @@ from . import _native as nv
 from .grafimo_errors import BGFileError, MotifFileFormatError, MotifFileReadError
 from .motif import Motif, is_motif_like
 from .motif_processing import (apply_pseudocount_jaspar_transfac_pfm, apply_pseudocount_meme,
-                               comp_pval_mat, compute_log_odds, get_uniform_bg, read_bg_file)
+                               comp_pval_mat, comp_pval_mat_many, compute_log_odds, get_uniform_bg,
+                               read_bg_file)
 from .utils import (DNA_ALPHABET, PSEUDOBG, RANGE, REV_COMPL, UNIF, almost_equal,
                     exception_handler, isListEqual)
 
@@ -473,8 +474,9 @@ def build_motif_meme(motif_file: str, bg_file: str, pseudocount: float, no_rever
                      cores: int, verbose: bool, debug: bool,
                      pvalue_matrix: bool = True) -> List[Motif]:
     """All motifs of a MEME file.  ``cores`` is accepted for signature compatibility: the
-    reference fans motif preprocessing out over a process pool (motif_ops.py:303-311); here the
-    expensive part (the DP) runs on the GPU, in the calling process."""
+    reference fans motif preprocessing out over a process pool (motif_ops.py:303-311); here
+    log-odds and scaling run on the host motif by motif, and the expensive part, the DP, runs
+    on the GPU for the whole file in one device pass (comp_pval_mat_many)."""
     _check_build_args(motif_file, bg_file, pseudocount, no_reverse, debug)
     if not isinstance(pseudocount, float):
         exception_handler(TypeError, f"Expected float, got {type(pseudocount).__name__}.\n", debug)
@@ -483,6 +485,7 @@ def build_motif_meme(motif_file: str, bg_file: str, pseudocount: float, no_rever
     bgs = _load_bg(bg_file, alphabet, no_reverse, debug)
     print(f"\nRead {len(raws)} motifs in {motif_file}")
     print("\nProcessing motifs\n")
+    t = time.time()
     motifs = []
     for raw in raws:
         width = int(raw.values.shape[1])
@@ -491,7 +494,12 @@ def build_motif_meme(motif_file: str, bg_file: str, pseudocount: float, no_rever
                                        alphabet, nucsmap, debug)
         motif = Motif(probs, width, alphabet, raw.motif_id, raw.motif_name, nucsmap)
         motif.set_bg(bgs)
-        motifs.append(_timed_process(motif, verbose, debug, pvalue_matrix))
+        motifs.append(process_motif_for_logodds(motif, debug, pvalue_matrix=False))
+    if pvalue_matrix:
+        for motif, pmf in zip(motifs, comp_pval_mat_many(motifs, debug)):
+            motif.set_motif_pval_matrix(pmf)
+    if verbose:
+        print("%d motifs processed in %.2fs" % (len(motifs), time.time() - t))
     return motifs
 
 

@@ -7,6 +7,8 @@ signatures and error behaviour; the two numeric ones are backed by libgrafimo_hi
   compute_log_odds -> gfm_compute_log_odds (host f64, libm log)      pyx:512-548 / :444-507
   comp_pval_mat    -> gfm_comp_pval_mat    (Staden DP ON THE GPU)    pyx:608-632 / :552-603
 
+plus comp_pval_mat_many, the DP of a whole motif set in one device pass (gfm_comp_pval_mat_many).
+
 The other four are tiny host-side table preparations kept in Python exactly as the
 reference has them (file parsing and 4xW elementwise arithmetic).
 """
@@ -150,3 +152,26 @@ def comp_pval_mat(motif, debug: bool) -> np.ndarray:
         raise AssertionError(nv.lib().gfm_last_error().decode())
     nv.check(rc)
     return out
+
+
+def comp_pval_mat_many(motifs, debug: bool) -> List[np.ndarray]:
+    """comp_pval_mat of a motif set in ONE device pass (gfm_comp_pval_mat_many: one DP launch, one workgroup per motif)
+    -> one f64 [1000*W + 1] per motif, in order, each bit-identical to comp_pval_mat(motif, debug)."""
+    motifs = list(motifs)
+    for motif in motifs:
+        if not motif.is_scaled:
+            exception_handler(MotifProcessingError,
+                              "The motif score matrix has not been scaled yet.\n", debug)
+    if not motifs:
+        return []
+    sms = [dense_score_matrix(m) for m in motifs]
+    widths = np.array([sm.shape[1] for sm in sms], dtype=np.int32)
+    sm_all = np.concatenate([sm.ravel() for sm in sms])
+    bgs = np.ascontiguousarray(np.stack([dense_bg(m) for m in motifs]))
+    sizes = nv.RANGE * widths.astype(np.int64) + 1
+    out = np.empty(int(sizes.sum()), dtype=np.float64)
+    rc = nv.lib().gfm_comp_pval_mat_many(len(motifs), nv.ptr(sm_all), nv.ptr(widths), nv.ptr(bgs), nv.ptr(out))
+    if rc == nv.GFM_ERR_ASSERT:
+        raise AssertionError(nv.lib().gfm_last_error().decode())
+    nv.check(rc)
+    return np.split(out, np.cumsum(sizes)[:-1])

@@ -356,7 +356,7 @@ def compute_results_many(motifs: List[Motif], sequence_loc: str, debug: bool, ar
         no_rows += "\nAre you using the correct VGs and searching on the right chromosomes?\n"
         if not files:
             exception_handler(ValueError, no_rows, debug)
-        dms = [DeviceMotif.from_motif(motifs[i]) for i in idxs]
+        dms = DeviceMotif.create_many([motifs[i] for i in idxs])     # one device pass for the width's handles
         try:
             try:
                 scan = StreamScan(dms, files, no_reverse, max(1, int(args_obj.cores)), threshold, qval_t, not no_qvalue)

@@ -81,6 +81,12 @@ int gfm_scale_pwm(const double *h_logodds, int width, int64_t *h_score_matrix_ou
  * (last DP row, un-normalised), bit-identical to the reference's. */
 int gfm_comp_pval_mat(const int64_t *h_score_matrix, int width, const double *h_bg,
                       double *h_pmf_out);
+/* The same for a motif set in one device pass (one DP launch, one workgroup per motif).
+ * h_score_matrices: the [4, W_i] matrices concatenated; h_bgs: [n_motifs][4];
+ * h_pmf_out: motif i at offset sum_{j<i} (1000*W_j + 1).  Every motif is checked before
+ * the device is touched; an error message names the failing motif's index. */
+int gfm_comp_pval_mat_many(int n_motifs, const int64_t *h_score_matrices, const int *widths,
+                           const double *h_bgs, double *h_pmf_out);
 
 /* ------------------------------------------------------------------ device-resident motif
  * The numeric content of a reference `Motif` (motif.py:18) that scoring reads:
@@ -95,6 +101,15 @@ typedef struct gfm_motif *gfm_motif_t;
 int gfm_motif_create(const int64_t *h_score_matrix, int width, const double *h_bg,
                      int min_val, int scale, double offset, const double *h_pmf,
                      gfm_motif_t *out);
+/* n_motifs handles in one device pass: one DP launch for the motifs whose h_pmfs[i] is NULL
+ * (h_pmfs itself may be NULL: every DP runs on device), one tail-table launch for all, one
+ * synchronisation.  Arrays as gfm_comp_pval_mat_many, min_vals / scales / offsets [n_motifs].
+ * Checks and codes are gfm_motif_create's, each message names the motif's index.  All or
+ * nothing: on failure every out[i] is NULL and nothing stays allocated.  Each handle is
+ * destroyed on its own (gfm_motif_destroy). */
+int gfm_motif_create_many(int n_motifs, const int64_t *h_score_matrices, const int *widths,
+                          const double *h_bgs, const int *min_vals, const int *scales,
+                          const double *offsets, const double *const *h_pmfs, gfm_motif_t *out);
 void gfm_motif_destroy(gfm_motif_t m);
 int gfm_motif_width(gfm_motif_t m);
 int gfm_motif_table_len(gfm_motif_t m); /* L */
