@@ -98,6 +98,9 @@ def get_parser():
     p.add_argument("-f", "--text-only", action="store_true", dest="text_only")
     p.add_argument("--recomb", action="store_true")
     p.add_argument("--qvalueT", action="store_true", dest="qval_t")
+    p.add_argument("--variant-effects", action="store_true", dest="variant_effects",
+                   help="also write grafimo_variant_effects[_MOTIF].tsv (printed with -f): the best REF and ALT hit of every "
+                        "variant site, rows kept on p < -t (graph routes only; no q-values, so not with --qvalueT)")
     p.add_argument("-j", "--cores", type=int, default=0, help="host threads for TSV ingest (0 = all)")
     p.add_argument("-o", "--out", default=DEFAULT_OUTDIR)
     p.add_argument("--verbose", action="store_true")
@@ -176,6 +179,11 @@ def main(argv=None):
         if len(set(a.chroms_find)) != len(a.chroms_find):
             sys.exit('ERROR: Duplicated chromosome names given to "--chroms-find"')
     from_graph = not from_vg and bool(a.linear_genome or a.vcf or a.bedfile)
+    if a.variant_effects and a.sequences:
+        sys.exit("ERROR: --variant-effects needs the graph (-g / -d with -b, or -l -v -b): the rows of -s carry no alleles")
+    if a.variant_effects and a.qval_t:
+        sys.exit("ERROR: --variant-effects has no q-values: its rows are kept on p < -t, which --qvalueT makes a q-value "
+                 "threshold (drop --qvalueT)")
     if not from_vg and (from_graph == bool(a.sequences) or (from_graph and not (a.linear_genome and a.vcf and a.bedfile))):
         sys.exit("ERROR: give -g XG / -d DIR with -b BED, or -s DIR, or all of -l FASTA -v VCF -b BED")
     if a.cores <= 0:
@@ -227,6 +235,22 @@ def main(argv=None):
             print_results(res, a.debug)
         else:
             write_results(res, motif, len(motifs), wf, a.debug)
+    if a.variant_effects:
+        from .variant_effects import compute_variant_effects_many, write_variant_effects
+        if from_vg:
+            from .extract_regions import read_manifest
+            manifest = read_manifest(sequences_loc)
+            if manifest is None:
+                sys.exit("ERROR: --variant-effects needs the graph; scan_graph left TSV rows, which carry no alleles")
+            effects = compute_variant_effects_many(motifs, manifest, None, a.debug, wf)
+        else:
+            effects = compute_variant_effects_many(motifs, graphs, region_lists, a.debug, wf)
+        for motif, table in zip(motifs, effects):
+            if a.text_only:                            # -f: printed like the report, no file written
+                print(table.to_string(index=False))
+                continue
+            path = write_variant_effects(table, motif, len(motifs), wf)
+            print(f"{len(table)} variant effect rows written to {path}")
     if sequences_loc:
         import shutil
         shutil.rmtree(sequences_loc, ignore_errors=True)

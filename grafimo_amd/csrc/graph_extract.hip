@@ -1287,6 +1287,10 @@ struct gfm_graph {
     // a gfm_graph_score / gfm_graph_annotate on another stream than the handle's last call waits for that call's work.
     hipStream_t f_last_stream = nullptr;
     hipEvent_t ev_call = nullptr;
+    // ---- gfm_graph_variant_effects: the windows of its last call (host list of (p, limit) pairs, device copy)
+    std::vector<long long> h_vwins;
+    void *v_wins = nullptr;
+    size_t v_cap = 0;
     bool call_pending = false;
     int serialise(hipStream_t st)
     {
@@ -1490,6 +1494,7 @@ GFM_API void gfm_graph_destroy(gfm_graph_t g)
     g->plans.clear();
     g->plan = nullptr;
     g->f_slabs.release();
+    if (g->v_wins) (void)hipFree(g->v_wins);
     delete g;
 }
 
@@ -2472,3 +2477,5 @@ GFM_API int gfm_graph_annotate(gfm_graph_t g, const void *d_hits, const uint64_t
     GX_TRY(hipGetLastError());
     return g->called(static_cast<hipStream_t>(stream));
 }
+
+#include "gfm_graph_variant.hpp"

@@ -557,6 +557,49 @@ int gfm_graph_hit_columns_wait(gfm_hit_columns_run_t run);
 int64_t gfm_region_labels(const char *chrom, const int64_t *h_starts, const int64_t *h_stops, int64_t n, char *h_out,
                           int64_t capacity);
 
+/* ------------------------------------------------------------------ per-variant motif effects
+ * Which variants create or destroy a binding site: for every graph site s (a substitution site with 1-3 ALT bases, an
+ * insertion, a deletion: the sites gfm_graph_create holds) and every allele a of it (0 = REF), the BEST k-mer among the rows
+ * the fused report would give at threshold 1 whose walk takes allele a at s AND covers the allele's footprint (the walk
+ * carries a haplotype constraint for s: SNV -- its base is in the window; deletion REF -- a deleted base is; deletion ALT
+ * -- the junction; insertion ALT -- an inserted base; insertion REF -- the anchor and the base behind it).  Best: highest
+ * score, then smallest start, smallest stop, '+' before '-', smallest k-mer as printed for its strand.
+ *
+ * gfm_graph_variant_effects: regions as gfm_graph_score takes them, motifs of ONE width; flags GFM_GRAPH_FORWARD_ONLY
+ *   (--no-reverse) and GFM_VARIANT_KEEP_ZERO_FREQ (--recomb: walks no haplotype carries count too).  Per motif m:
+ *   d_keys[m] uint64 [n_sites][4] zeroed by the caller (the packed best key of every (site, allele): pass 1);
+ *   d_recs[m] gfm_variant_rec_t [rec_capacity[m]] and *d_rec_count[m] (zeroed by the caller): pass 2 appends EVERY walk
+ *   and strand whose key equals its slot's best (records beyond the capacity are counted, not stored: call again with the
+ *   count as capacity and fresh buffers).  *d_overflow (zeroed by the caller) = 1 if a window holds more than 2^24 walks
+ *   (its walks are left out: the table is not complete).  *n_windows (host, optional) = windows enumerated: only those
+ *   within reach of a site.  Enqueue only (host work: the window list; the handle's calls are serialised as
+ *   gfm_graph_score's are).
+ * gfm_variant_effect_columns (host, no device touched): the records of ONE motif and graph -> one row per (site, ALT
+ *   allele) in site order, kept when either side's p-value < threshold (strict, as the report) or, with
+ *   GFM_VARIANT_ALL_SITES, whenever either allele has a qualifying k-mer.  Per row: o_site, o_alt (1..3); per side
+ *   k = 0 REF, 1 ALT at [2 * row + k]: o_found (0: no qualifying k-mer -- the other columns of that side are NaN / 0),
+ *   o_score (log-odds: scaled / scale + width * offset), o_pvalue (h_ptable[scaled]), o_start, o_stop, o_strand (0 '+',
+ *   1 '-'), o_kmers [W + 1] with a '\n' behind; o_effect: 0 none, 1 gain (ALT only), 2 loss (REF only), 3 both.  Rows
+ *   are at most the sum of h_n_alts; *n_out = rows written. */
+#define GFM_VARIANT_KEEP_ZERO_FREQ 2u
+#define GFM_VARIANT_ALL_SITES 1u
+typedef struct gfm_variant_rec {
+    int32_t slot;       /* site * 4 + allele */
+    int32_t score;      /* scaled score */
+    int64_t start, stop;
+    uint8_t strand, pad[7];
+    uint8_t kmer[GFM_MAX_WIDTH];
+} gfm_variant_rec_t;
+int gfm_graph_variant_effects(gfm_graph_t g, const gfm_motif_t *motifs, int32_t n_motifs, int32_t n_regions,
+                              const int64_t *h_starts, const int64_t *h_stops, uint32_t flags, uint64_t *const *d_keys,
+                              void *const *d_recs, const int64_t *rec_capacity, uint64_t *const *d_rec_count,
+                              int32_t *d_overflow, int64_t *n_windows, void *stream);
+int gfm_variant_effect_columns(const double *h_ptable, int32_t table_len, int32_t scale, double offset, int32_t width,
+                               int32_t n_sites, const uint8_t *h_n_alts, const gfm_variant_rec_t *h_recs, int64_t n_recs,
+                               double threshold, uint32_t flags, int64_t *n_out, int32_t *o_site, int32_t *o_alt,
+                               uint8_t *o_found, double *o_score, double *o_pvalue, int64_t *o_start, int64_t *o_stop,
+                               uint8_t *o_strand, uint8_t *o_kmers, uint8_t *o_effect);
+
 /* Phased VCF (plain or gzip/bgzip) -> the site arrays of gfm_graph_create for one chromosome; host
  * threads parse the lines.  The reference hands the VCF to `vg construct` / `vg index -G`
  * (constructVG.py:332,394); here every ALT allele is taken apart: single-base substitutions (one site per
