@@ -101,6 +101,9 @@ def get_parser():
     p.add_argument("--variant-effects", action="store_true", dest="variant_effects",
                    help="also write grafimo_variant_effects[_MOTIF].tsv (printed with -f): the best REF and ALT hit of every "
                         "variant site, rows kept on p < -t (graph routes only; no q-values, so not with --qvalueT)")
+    p.add_argument("--haplotype-hits", action="store_true", dest="haplotype_hits",
+                   help="also write grafimo_haplotype_hits[_MOTIF].tsv (printed with -f): per region, how many of the report's "
+                        "rows each haplotype carries, one column per haplotype (graph routes only)")
     p.add_argument("-j", "--cores", type=int, default=0, help="host threads for TSV ingest (0 = all)")
     p.add_argument("-o", "--out", default=DEFAULT_OUTDIR)
     p.add_argument("--verbose", action="store_true")
@@ -184,6 +187,8 @@ def main(argv=None):
     if a.variant_effects and a.qval_t:
         sys.exit("ERROR: --variant-effects has no q-values: its rows are kept on p < -t, which --qvalueT makes a q-value "
                  "threshold (drop --qvalueT)")
+    if a.haplotype_hits and a.sequences:
+        sys.exit("ERROR: --haplotype-hits needs the graph (-g / -d with -b, or -l -v -b): the rows of -s carry no walks")
     if not from_vg and (from_graph == bool(a.sequences) or (from_graph and not (a.linear_genome and a.vcf and a.bedfile))):
         sys.exit("ERROR: give -g XG / -d DIR with -b BED, or -s DIR, or all of -l FASTA -v VCF -b BED")
     if a.cores <= 0:
@@ -251,6 +256,22 @@ def main(argv=None):
                 continue
             path = write_variant_effects(table, motif, len(motifs), wf)
             print(f"{len(table)} variant effect rows written to {path}")
+    if a.haplotype_hits:
+        from .haplotype_hits import compute_haplotype_hits_many, print_haplotype_hits, write_haplotype_hits
+        if from_vg:
+            from .extract_regions import read_manifest
+            manifest = read_manifest(sequences_loc)
+            if manifest is None:
+                sys.exit("ERROR: --haplotype-hits needs the graph; scan_graph left TSV rows, which carry no walks")
+            matrices = compute_haplotype_hits_many(motifs, manifest, None, a.debug, wf)
+        else:
+            matrices = compute_haplotype_hits_many(motifs, graphs, region_lists, a.debug, wf)
+        for motif, hh in zip(motifs, matrices):
+            if a.text_only:                            # -f: printed like the report, no file written
+                print_haplotype_hits(hh)
+                continue
+            path = write_haplotype_hits(hh, motif, len(motifs), wf)
+            print(f"{hh.counts.shape[0]} x {hh.counts.shape[1]} haplotype hit counts written to {path}")
     if sequences_loc:
         import shutil
         shutil.rmtree(sequences_loc, ignore_errors=True)

@@ -108,6 +108,19 @@ def _load_npz_mapped(path: str):
     return out
 
 
+def _vcf_sample_names(path: str) -> List[str]:
+    """the sample columns of a VCF's #CHROM line (plain or gzip / bgzip; the header is read, nothing behind it)"""
+    with open(path, "rb") as fh:
+        gz = fh.read(2) == b"\x1f\x8b"
+    with (gzip.open(path, "rt", errors="replace") if gz else open(path, "rt", errors="replace")) as fh:
+        for line in fh:
+            if line.startswith("#CHROM"):
+                return line.rstrip("\r\n").split("\t")[9:]
+            if not line.startswith("#"):
+                break
+    return []
+
+
 def _read_fasta_record(path: str, chrom: str) -> np.ndarray:
     """Bases of one record as uppercase uint8.  The file is mapped and only header lines are looked at
     (a genome FASTA is gigabytes; the record wanted is one chromosome), or `path.fai` is used."""
@@ -153,8 +166,11 @@ class GraphIndex:
     alternate allele, the bitset of haplotypes that carry it."""
 
     def __init__(self, chrom: str, ref: np.ndarray, pos, n_alts, alt_bases, alt_bits, n_haplotypes: int,
-                 skipped: int = 0, del_len=None, ins_len=None, ins_off=None, ins_bases=None):
+                 skipped: int = 0, del_len=None, ins_len=None, ins_off=None, ins_bases=None, sample_names=None):
         self.chrom = chrom
+        # the VCF samples in file order (haplotypes 2k and 2k + 1 are sample k's), or None when unknown (vg's files, older
+        # indexes): the column names of the per-haplotype hit matrix (haplotype_hits.py)
+        self.sample_names = None if sample_names is None else [str(x) for x in sample_names]
         self.ref = np.ascontiguousarray(ref, dtype=np.uint8)
         self.pos = np.ascontiguousarray(pos, dtype=np.int32)
         # 0 for a SNP site; for a deletion the number of bases removed after the anchor `pos`
@@ -234,8 +250,10 @@ class GraphIndex:
         if V == 0:
             print(f"WARNING: no usable VCF record for chromosome {chrom!r} in {vcf}: the graph is the bare reference "
                   f"(do the chromosome names of the VCF and the FASTA match?)", file=sys.stderr)
+        samples = _vcf_sample_names(vcf)
         return cls(chrom, ref, pos, n_alts, alt_bases, bits, int(H.value), int(skipped.value), del_len=del_len,
-                   ins_len=ins_len, ins_off=ins_off, ins_bases=ins_bases)
+                   ins_len=ins_len, ins_off=ins_off, ins_bases=ins_bases,
+                   sample_names=samples if samples and 2 * len(samples) == int(H.value) else None)
 
     @classmethod
     def from_vg(cls, xg: str, gbwt: Optional[str] = None, chrom: Optional[str] = None, path_name: Optional[str] = None) -> "GraphIndex":
@@ -258,6 +276,8 @@ class GraphIndex:
                       n_alts=self.n_alts, alt_bases=self.alt_bases, n_haplotypes=np.int64(self.n_haplotypes),
                       skipped=np.int64(self.skipped), ins_len=self.ins_len, ins_off=self.ins_off, ins_bases=self.ins_bases,
                       alt_bits=self.alt_bits if self.alt_bits is not None else np.empty(0, np.uint64))
+        if self.sample_names:                           # optional member: indexes without it load with sample_names None
+            arrays["sample_names"] = np.array(self.sample_names, dtype=str)
         # written beside its place and moved there: a file that is being read through a mapping (load() of this very path, in this
         # process or another) must not be truncated under the reader -- the rename leaves the old pages to those who mapped them
         tmp = f"{path}.{os.getpid()}.tmp"
@@ -293,7 +313,7 @@ class GraphIndex:
         bits = z["alt_bits"] if z["alt_bits"].size else None
         idx = cls(str(z["chrom"]), z["ref"], z["pos"], z["n_alts"], z["alt_bases"], bits, int(z["n_haplotypes"]),
                   int(z["skipped"]), del_len=z["del_len"], ins_len=z["ins_len"], ins_off=z["ins_off"],
-                  ins_bases=z["ins_bases"])
+                  ins_bases=z["ins_bases"], sample_names=z["sample_names"].tolist() if "sample_names" in z else None)
         idx._mapping = z.get("__mapping__")             # (keeps the file mapping alive as long as the arrays)
         return idx
 
@@ -612,7 +632,8 @@ def shard_index(index: GraphIndex, starts, stops, max_width: int = nv.GFM_MAX_WI
     sub = GraphIndex(index.chrom, index.ref, index.pos[keep], index.n_alts[keep], index.alt_bases[keep],
                      index.alt_bits[keep] if index.alt_bits is not None else None, index.n_haplotypes, index.skipped,
                      del_len=index.del_len[keep], ins_len=ins_len, ins_off=ins_off,
-                     ins_bases=np.ascontiguousarray(index.ins_bases[src]) if total else np.zeros(0, dtype=np.uint8))
+                     ins_bases=np.ascontiguousarray(index.ins_bases[src]) if total else np.zeros(0, dtype=np.uint8),
+                     sample_names=index.sample_names)
     sub.shard_of = (n, int(keep.sum()))
     return sub
 

@@ -500,6 +500,18 @@ int gfm_graph_profile_enable(gfm_graph_t g, int on);
 int gfm_graph_profile_read(gfm_graph_t g, float *h_ms_out, int capacity, int *n_out);
 int gfm_graph_annotate(gfm_graph_t g, const void *d_hits, const uint64_t *d_hit_count, int64_t hit_capacity,
                        const int32_t *d_cutoff, const double *d_qtable, void *d_records, void *stream);
+/* The per-haplotype hit matrix of the entries of the LAST gfm_graph_score[_multi] call, the same list gfm_graph_annotate
+ * serves: for region r of that call (0 .. n_regions - 1, the call's region list) and haplotype h of the graph (its bitset
+ * order), d_counts[r * n_hap + h] = the entries with score >= *d_cutoff (d_cutoff NULL: all; --qvalueT as in annotate) of
+ * region r whose walk h carries -- h is in the AND of the bitsets of the walk's allele constraints, the set whose size is
+ * the record's freq -- and d_best[r * n_hap + h] = the highest scaled score among them (-1: none).  int32 [n_regions][n_hap]
+ * each, device memory, overwritten.  scratch_bytes bounds the device scratch of the carrier masks (<= 0: 256 MB): the
+ * entries are grouped by region on the device and taken in batches whose masks fit it; the result does not depend on it.
+ * GFM_ERR_INVALID when the graph carries no haplotypes, n_regions is not that of the last call, or an output is NULL.
+ * Enqueue only (stream-ordered device scratch); calls of one handle are serialised as gfm_graph_score's are. */
+int gfm_graph_haplotype_hits(gfm_graph_t g, const void *d_hits, const uint64_t *d_hit_count, int64_t hit_capacity,
+                             const int32_t *d_cutoff, int32_t n_regions, int32_t *d_counts, int32_t *d_best,
+                             int64_t scratch_bytes, void *stream);
 
 /* ------------------------------------------------------------------ the report's rows from the hit records (host)
  * replaces what ResultTmp.to_df does with the rows that passed the threshold (resultsTmp.py:303-314): the --recomb filter

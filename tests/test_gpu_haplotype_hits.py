@@ -1,0 +1,231 @@
+"""Per-haplotype hit matrix on the GPU (gfm_graph_haplotype_hits -> grafimo_amd.haplotype_hits) against the haplotype brute
+force of tests/haplotype_bruteforce.py, the report's own rows, the two tutorial routes and the CLI."""
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pandas as pd
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+from extract_helpers import make_consistent_graph_files, motif_as_oracle_dict  # noqa: E402
+from haplotype_bruteforce import haplotype_matrix, integer_cutoff  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+GOLD = os.path.join(ROOT, "tests", "golden", "ref_data")
+
+
+class _Args:
+    def __init__(self, threshold=1e-4, no_reverse=False, recomb=False, qvalue_t=False, no_qvalue=True):
+        self.threshold, self.noreverse, self.recomb = threshold, no_reverse, recomb
+        self.noqvalue, self.qvalueT = no_qvalue, qvalue_t
+
+
+def _motif(W, seed=0):
+    from grafimo_amd import synth
+    rec = synth.synthetic_motif(W, np.random.default_rng(900 + 13 * W + seed), np.array([0.3, 0.2, 0.2, 0.3]))
+    return synth.motif_object(rec, f"SYN{W}")
+
+
+def _check_bruteforce(hh, idx, regions, motif, args):
+    od = motif_as_oracle_dict(motif)
+    W = od["width"]
+    ptab = np.cumsum(od["pmf"][::-1])[::-1]
+    counts, best = haplotype_matrix(idx, regions, W, od["score_matrix"], od["min_val"], integer_cutoff(ptab, args.threshold),
+                                    forward_only=args.noreverse)
+    assert hh.counts.shape == counts.shape and hh.counts.dtype == np.int32
+    assert (hh.counts == counts).all(), np.argwhere(hh.counts != counts)[:5]
+    some = best >= 0
+    assert (hh.best == np.where(some, best, -1)).all()
+    exp_score = np.where(some, best / od["scale"] + W * od["offset"], np.nan)
+    assert np.array_equal(hh.best_score, exp_score, equal_nan=True)
+    exp_p = np.where(some, ptab[np.where(some, best, 0)], np.nan)
+    assert np.allclose(hh.best_pvalue, exp_p, rtol=1e-12, atol=0, equal_nan=True)
+    return counts
+
+
+@pytest.mark.parametrize("seed,W,kinds,no_reverse,threshold", [
+    (1, 5, "sidmDOc", False, 1e-2), (2, 8, "sidmDOc", True, 1e-2), (3, 19, "sidmDOc", False, 1e-4), (4, 19, "sid", True, 1e-2),
+    (5, 30, "sidmDOc", False, 1e-2), (6, 64, "sidmDOc", False, 1e-4), (7, 12, "sidD", False, 1e-4)])
+def test_bruteforce_parity(tmp_path, seed, W, kinds, no_reverse, threshold):
+    from grafimo_amd.extract_regions import GraphIndex
+    from grafimo_amd.haplotype_hits import compute_haplotype_hits
+    fa, vcf = make_consistent_graph_files(str(tmp_path), length=500, n_samples=12, seed=seed, kinds=kinds)
+    idx = GraphIndex.from_fasta_vcf(fa, vcf, "c")
+    p = idx.pos
+    regions = [(0, int(p[len(p) // 3]) + 1), (int(p[len(p) // 3]) - 2, int(p[2 * len(p) // 3])), (int(p[-3]), 500), (0, 500),
+               (3, 4)]
+    args = _Args(threshold=threshold, no_reverse=no_reverse)
+    motif = _motif(W, seed)
+    hh = compute_haplotype_hits(motif, idx, regions, False, args)
+    counts = _check_bruteforce(hh, idx, regions, motif, args)
+    if threshold == 1e-2:
+        assert counts.sum() > 0
+    assert hh.haplotype_names == [f"s{k}|{j}" for k in range(12) for j in (1, 2)]
+    assert hh.region_names.tolist() == [f"c:{S}-{E}" for S, E in regions]
+
+
+@pytest.mark.parametrize("n_samples", [3, 65])
+def test_haplotype_counts_off_the_word(tmp_path, n_samples):
+    """H = 6 and H = 130: not a multiple of 64, and more than one word -- no tail bit may leak into a count"""
+    from grafimo_amd.extract_regions import GraphIndex
+    from grafimo_amd.haplotype_hits import compute_haplotype_hits
+    fa, vcf = make_consistent_graph_files(str(tmp_path), length=400, n_samples=n_samples, seed=40 + n_samples, kinds="sidmDO")
+    idx = GraphIndex.from_fasta_vcf(fa, vcf, "c")
+    assert idx.n_haplotypes == 2 * n_samples
+    args = _Args(threshold=1e-2)
+    motif = _motif(8, n_samples)
+    hh = compute_haplotype_hits(motif, idx, [(0, 200), (150, 400)], False, args)
+    assert hh.counts.shape == (2, 2 * n_samples)
+    assert _check_bruteforce(hh, idx, [(0, 200), (150, 400)], motif, args).sum() > 0
+
+
+@pytest.mark.parametrize("qvalue_t", [False, True])
+def test_sums_equal_report_frequencies_and_recomb_changes_nothing(tmp_path, qvalue_t):
+    from grafimo_amd.extract_regions import GraphIndex, compute_results_from_graph
+    from grafimo_amd.haplotype_hits import compute_haplotype_hits
+    fa, vcf = make_consistent_graph_files(str(tmp_path), length=600, n_samples=10, seed=17, kinds="sidmDOc")
+    idx = GraphIndex.from_fasta_vcf(fa, vcf, "c")
+    regions = [(0, 250), (200, 600), (100, 101), (300, 450)]
+    motif = _motif(8, 5)
+    # (q-values of random sequence are high: q < 0.9 keeps a few dozen of the ~2 900 rows with p < 0.9)
+    args = _Args(threshold=0.9 if qvalue_t else 1e-2, qvalue_t=qvalue_t, no_qvalue=False)
+    hh = compute_haplotype_hits(motif, idx, regions, False, args)
+    rep = compute_results_from_graph(motif, idx, regions, False, args)
+    freq = rep.groupby("sequence_name")["haplotype_frequency"].sum()
+    sums = hh.counts.sum(axis=1)
+    assert sums.sum() > 0
+    for name, s in zip(hh.region_names, sums):
+        assert s == int(freq.get(name, 0)), name
+    # best: the highest score among the region's report rows that the haplotype carries -- at most the region's best row
+    for r, name in enumerate(hh.region_names):
+        part = rep[rep["sequence_name"] == name]
+        top = part["score"].max() if len(part) else np.nan
+        have = hh.best_score[r][hh.counts[r] > 0]
+        assert len(have) == 0 or have.max() <= top
+    rc = _Args(threshold=args.threshold, qvalue_t=qvalue_t, no_qvalue=False, recomb=True)
+    again = compute_haplotype_hits(motif, idx, regions, False, rc)
+    assert (again.counts == hh.counts).all() and (again.best == hh.best).all()
+
+
+def test_tiny_scratch_equals_default(tmp_path):
+    from grafimo_amd.extract_regions import GraphIndex
+    from grafimo_amd.haplotype_hits import compute_haplotype_hits
+    fa, vcf = make_consistent_graph_files(str(tmp_path), length=600, n_samples=40, seed=23, kinds="sidmDOc")
+    idx = GraphIndex.from_fasta_vcf(fa, vcf, "c")
+    regions = [(0, 300), (250, 600), (0, 600)]
+    motif = _motif(8, 2)
+    args = _Args(threshold=0.05)
+    ref = compute_haplotype_hits(motif, idx, regions, False, args)
+    assert ref.counts.sum() > 100
+    hw = (idx.n_haplotypes + 63) // 64
+    for entries in (1, 3, 17):
+        small = compute_haplotype_hits(motif, idx, regions, False, args, scratch_bytes=entries * (8 * hw + 4))
+        assert (small.counts == ref.counts).all() and (small.best == ref.best).all(), entries
+
+
+def test_many_equals_single_and_graph_lists(tmp_path):
+    from grafimo_amd.extract_regions import GraphIndex
+    from grafimo_amd.haplotype_hits import compute_haplotype_hits, compute_haplotype_hits_many
+    fa, vcf = make_consistent_graph_files(str(tmp_path), length=500, n_samples=12, seed=29, kinds="sidD")
+    idx = GraphIndex.from_fasta_vcf(fa, vcf, "c")
+    motifs = [_motif(8, 1), _motif(12, 2), _motif(8, 3), _motif(5, 4), _motif(8, 5), _motif(8, 6)]
+    args = _Args(threshold=0.05)
+    regions = [(0, 300), (200, 500)]
+    many = compute_haplotype_hits_many(motifs, idx, regions, False, args)
+    for m, t in zip(motifs, many):
+        one = compute_haplotype_hits(m, idx, regions, False, args)
+        assert t.motif_id == m.motif_id
+        assert (t.counts == one.counts).all() and (t.best == one.best).all()
+    # a list of entries that share one graph: rows in the caller's entry order
+    split = compute_haplotype_hits(motifs[0], [idx, idx], [[regions[1]], [regions[0]]], False, args, chrom_names=["c", "c"])
+    assert (split.counts == many[0].counts[::-1]).all() and split.region_names.tolist() == many[0].region_names.tolist()[::-1]
+    named = compute_haplotype_hits(motifs[0], idx, regions, False, args, haplotype_names=[f"h{k}" for k in range(24)])
+    assert named.haplotype_names[0] == "h0" and (named.counts == many[0].counts).all()
+
+
+def test_graph_without_haplotypes_is_refused():
+    from grafimo_amd.extract_regions import GraphIndex
+    from grafimo_amd.haplotype_hits import compute_haplotype_hits
+    ref = np.frombuffer(b"ACGT" * 25, dtype=np.uint8)
+    idx = GraphIndex("c", ref, np.array([10], np.int32), np.array([1], np.uint8), np.array([[ord("A"), 0, 0]], np.uint8), None, 0)
+    with pytest.raises(ValueError, match="carries no haplotypes"):
+        compute_haplotype_hits(_motif(8), idx, [(0, 100)], False, _Args(threshold=1.0))
+
+
+@pytest.fixture()
+def mygenome(tmp_path, monkeypatch):
+    import shutil
+    g = tmp_path / "data" / "mygenome"
+    shutil.copytree(os.path.join(GOLD, "mygenome"), g)     # (scan_graph saves x.gfmidx.npz beside x.xg)
+    monkeypatch.setenv("GRAFIMO_INDEX_CACHE", str(tmp_path / "cache"))
+    monkeypatch.delenv("GRAFIMO_SCAN_OUTPUT", raising=False)
+    return str(g)
+
+
+def test_manifest_route_equals_fasta_vcf_route(tmp_path, mygenome, monkeypatch):
+    """vg's x.xg + x.gbwt through scan_graph's manifest against xy.fa + xy2.vcf.gz: the same matrix, columns hap<k> against
+    the VCF's sample names"""
+    import contextlib
+    import io
+    import shutil
+    from grafimo_amd.extract_regions import DeviceGraph, GraphIndex, read_bed_regions, read_manifest, scan_graph
+    from grafimo_amd.haplotype_hits import compute_haplotype_hits
+    from grafimo_amd.motif_ops import get_motif_pwm
+    from grafimo_amd.workflow import Findmotif
+    bed = os.path.join(tmp_path, "x.bed")
+    with open(os.path.join(GOLD, "regions.bed")) as src, open(bed, "w") as dst:
+        dst.writelines(line for line in src if line.startswith("chrx\t"))
+    wf = Findmotif(graph_genome_dir=mygenome, bedfile=bed, cores=2, threshold=0.05)
+    motif = get_motif_pwm(os.path.join(GOLD, "example.meme"), wf, 2, True, pvalue_matrix=False)[0]
+    monkeypatch.setenv("GRAFIMO_SCAN_OUTPUT", "manifest")
+    with contextlib.redirect_stdout(io.StringIO()):
+        loc = scan_graph({motif.width}, wf, True)
+    try:
+        man = read_manifest(loc)
+        assert man is not None and [e["chrom"] for e in man["entries"]] == ["x"]
+        args = _Args(threshold=0.05)
+        a = compute_haplotype_hits(motif, man, None, False, args)
+        idx = GraphIndex.from_fasta_vcf(os.path.join(GOLD, "xy.fa"), os.path.join(GOLD, "xy2.vcf.gz"), "x")
+        b = compute_haplotype_hits(motif, DeviceGraph(idx), read_bed_regions(bed)["chrx"], False, args)
+        assert a.haplotype_names == ["hap0", "hap1"] and b.haplotype_names == ["1|1", "1|2"]
+        assert a.region_names.tolist() == b.region_names.tolist()
+        assert (a.counts == b.counts).all() and (a.best == b.best).all() and a.counts.sum() > 0
+    finally:
+        shutil.rmtree(loc, ignore_errors=True)
+
+
+def test_cli_writes_matrix_and_leaves_report_alone(tmp_path):
+    base = [sys.executable, "-m", "grafimo_amd", "-m", os.path.join(GOLD, "MA0139.1.meme"), "-l", os.path.join(GOLD, "xy.fa"),
+            "-v", os.path.join(GOLD, "xy2.vcf.gz"), "-b", os.path.join(GOLD, "regions.bed"), "-t", "0.05"]
+    a, b = str(tmp_path / "a"), str(tmp_path / "b")
+    env = dict(os.environ, PYTHONPATH=ROOT)
+    subprocess.run(base + ["-o", a], check=True, cwd=str(tmp_path), env=env, timeout=600)
+    r = subprocess.run(base + ["-o", b, "--haplotype-hits"], check=True, cwd=str(tmp_path), env=env, timeout=600,
+                       capture_output=True, text=True)
+    fa, fb = sorted(os.listdir(a)), sorted(os.listdir(b))
+    assert fb == sorted(fa + ["grafimo_haplotype_hits.tsv"])
+    for f in fa:
+        assert open(os.path.join(a, f), "rb").read() == open(os.path.join(b, f), "rb").read(), f
+    assert "haplotype hit counts written to" in r.stdout
+    t = pd.read_csv(os.path.join(b, "grafimo_haplotype_hits.tsv"), sep="\t")
+    assert list(t.columns) == ["motif_id", "motif_alt_id", "sequence_name", "1|1", "1|2"]
+    # the same matrix through the Python interface
+    from grafimo_amd.extract_regions import GraphIndex, read_bed_regions
+    from grafimo_amd.haplotype_hits import compute_haplotype_hits_many
+    from grafimo_amd.motif_ops import build_motif_meme_host
+    motif = build_motif_meme_host(os.path.join(GOLD, "MA0139.1.meme"), "unfrm_dst", 0.1, False)[0]
+    bed = read_bed_regions(os.path.join(GOLD, "regions.bed"))
+    graphs = [GraphIndex.from_fasta_vcf(os.path.join(GOLD, "xy.fa"), os.path.join(GOLD, "xy2.vcf.gz"), c[3:]) for c in bed]
+    hh = compute_haplotype_hits_many([motif], graphs, [bed[c] for c in bed], False, _Args(threshold=0.05, no_qvalue=False))[0]
+    pd.testing.assert_frame_equal(t, hh.to_frame(), check_dtype=False)
+    assert hh.counts.sum() > 0
+    # -f prints the table instead of writing it
+    r = subprocess.run(base + ["-o", str(tmp_path / "c"), "-f", "--haplotype-hits"], check=True, cwd=str(tmp_path), env=env,
+                       timeout=600, capture_output=True, text=True)
+    assert "motif_id\tmotif_alt_id\tsequence_name\t1|1\t1|2\n" in r.stdout
+    assert not os.path.exists(tmp_path / "c" / "grafimo_haplotype_hits.tsv")
