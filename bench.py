@@ -1,7 +1,11 @@
 #!/usr/bin/env python3
 """bench.py -- scored haplotype k-mers/s of the MI355X scoring path (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W [--config 2|3|4|5]
+    python bench.py --gpus N --steps K --warmup W [--config 2|3|4|5] [--full]
+
+A plain run does what the headline figure needs and nothing else: it sets up, warms up, times the K steps, writes
+--dump-outputs if asked and prints the result line.  --full adds every side measurement and self-check listed below
+(CPU baselines, the oracle slice, the other configs and paths); the blocks of the line that a plain run leaves out are null.
 
 With N > 1 and no WORLD_SIZE in the environment this process touches no GPU: it starts the N ranks itself
 (python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py <same flags>),
@@ -31,11 +35,15 @@ With --dump-outputs DIR rank 0 also writes what the last timed step computed (se
 Beside the contract's fields the line carries
   roofline            the score kernel alone: HIP events riding on its dispatch packets, sampled inside the timed
                       bursts; `peak` = 8 TB/s vendor, `peak_measured` = this device's bare interleaved stream of
-                      the same byte mix (gfm_calibrate_stream), `frac_of_measured`; `traffic` from the committed PMC
-                      passes (`traffic_source` says so);
+                      the same byte mix (gfm_calibrate_stream, --full), `frac_of_measured`; `traffic` from the committed
+                      PMC passes (`traffic_source` says so);
   tail_ms             post kernel + [all-reduce] + q-table [+ selection on q] [+ gather], events on the tail stream;
   rank_ms_per_step    every rank's own median ms per step; rccl_world = dist.get_world_size();
-  N = 1, default config only (each can be switched off):
+  --full only:
+  config.oracle_checked_rows   a slice of the last timed step's scores checked against the CPU oracle (0 without --full);
+  product_paths       N > 1 (or --force-dist), configs 2 / 3: the fused graph path and the streamed scan under the
+                      run's process group (--no-extras switches it off);
+  --full, N = 1, default config only (each can be switched off):
   roofline_config3    >= 10 steps of the config-3 shard (1.25e8 windows generated on the device, `nt` stores: 477 MiB
                       of scores per launch, beyond any cache) -- also the 1-GPU point of the N > 1 curve
                       (`scaling_curve_point` names the curve's workload and this N's value on it at every N);
@@ -996,13 +1004,18 @@ def main():
                     help="split the --steps timed steps into this many bursts; the median ms per step is reported")
     ap.add_argument("--rows", type=int, default=None, help="override the rows per GPU (diagnostics)")
     ap.add_argument("--threshold", type=float, default=1e-4)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-e2e", action="store_true")
-    ap.add_argument("--no-e2e-large", action="store_true", help="skip the 2e7-row / 10 000-file TSV directory")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every side measurement and self-check (CPU baselines, oracle slice, other configs and "
+                         "paths); a plain run measures the headline figure only")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-e2e", action="store_true", help="with --full: skip the TSV-directory scans")
+    ap.add_argument("--no-e2e-large", action="store_true", help="with --full: skip the 2e7-row / 10 000-file TSV directory")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip roofline_config3, sustained, peak_measured and extract (N=1 default config only)")
+                    help="with --full: skip roofline_config3, sustained, peak_measured and extract (N=1 default config "
+                         "only) and product_paths (N > 1)")
     ap.add_argument("--sustained-s", type=float, default=5.0, help="length of the sustained leg in seconds")
-    ap.add_argument("--no-config45", action="store_true", help="skip the roofline_config4 / roofline_config5 blocks of the default line")
+    ap.add_argument("--no-config45", action="store_true",
+                    help="with --full: skip the roofline_config4 / roofline_config5 blocks of the default line")
     ap.add_argument("--slots", type=int, default=3,
                     help="buffer slots of the scan pipeline (2: the device waits for slot reuse; >= 3: the host does)")
     ap.add_argument("--score-buffers", type=int, default=0,
@@ -1060,9 +1073,10 @@ def main():
         n = len(host_batch)
 
     # ---- everything that forks workers comes BEFORE the first HIP call
-    default_n1 = rank == 0 and world == 1 and cfg == 2 and not args.rows
+    # default_n1: the side blocks of the default N = 1 line are run (--full only)
+    default_n1 = args.full and rank == 0 and world == 1 and cfg == 2 and not args.rows
     cpu = {}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baselines(mots[0])
     tsv_dirs = {}
     try:
@@ -1190,15 +1204,19 @@ def run_rank(args, cfg, rank, local_rank, world, mots, ctcf, n, host_batch, on_q
         dist.all_gather(rank_ms, mine)
     rank_ms = [float(t.item()) for t in rank_ms]
 
-    # outputs of the last step stay valid: self-checks outside the timed region (the CPU oracle as the checker)
-    from oracle import oracle as orc
-    orc.build()
-    checked_rows = 1_000_000
+    # outputs of the last step stay valid: self-checks outside the timed region -- the counts always, with --full also a
+    # slice of the scores against the CPU oracle (the checker)
+    checked_rows = 1_000_000 if args.full else 0
+    if checked_rows:
+        from oracle import oracle as orc
+        orc.build()
     if cfg == 5:
         torch.cuda.synchronize(dev)
         for w in widths:
             nr = scanners[w].nrows.cpu().numpy()
             assert (nr == n * world).all(), (w, nr, n, world)
+            if not checked_rows:
+                continue
             km = bufs[w][0][:checked_rows].cpu().numpy()
             for k, j in enumerate(groups[w]):        # a slice of every motif's scores against the oracle
                 _, pt = dms[j].tables()
@@ -1210,17 +1228,18 @@ def run_rank(args, cfg, rank, local_rank, world, mots, ctcf, n, host_batch, on_q
         res = scanner.collect(last)
         n_hits = int(len(res["rows"]))
         assert res["n_scored"] == n * world, (res["n_scored"], n, world)
-        km = bufs[(it - 1) % rotate][:checked_rows].cpu().numpy()
-        _, pt = dms[0].tables()
-        exp, _ = orc.score_kmers_table(km, mots[0]["sm"], pt, mots[0]["min_val"])
-        assert np.array_equal(last.scores[:len(km)].cpu().numpy(), exp), "scores differ from the oracle"
+        if checked_rows:
+            km = bufs[(it - 1) % rotate][:checked_rows].cpu().numpy()
+            _, pt = dms[0].tables()
+            exp, _ = orc.score_kmers_table(km, mots[0]["sm"], pt, mots[0]["min_val"])
+            assert np.array_equal(last.scores[:len(km)].cpu().numpy(), exp), "scores differ from the oracle"
     assert n_hits > 0
     if args.dump_outputs and rank == 0:      # before the blocks below run further steps on these buffers
         dump_outputs(args.dump_outputs, multi_outputs(scanners, groups, len(mots), n) if cfg == 5
                      else scan_outputs(res, last.scores[:n]))
 
     extras = {}
-    if use_dist and cfg in (2, 3) and not args.no_extras:
+    if args.full and use_dist and cfg in (2, 3) and not args.no_extras:
         # the two other PRODUCT paths under the same process group, so that a scaling run says something about all three: the
         # fused graph path (every rank uploads its shard of the graph) and the streamed TSV scan (every rank its files)
         #  the block decides about failures COLLECTIVELY, stage by stage: see product_paths_block
@@ -1490,6 +1509,7 @@ def run_rank(args, cfg, rank, local_rank, world, mots, ctcf, n, host_batch, on_q
                 "qvalues": True,
                 "hits_last_step": n_hits,
                 "oracle_checked_rows": checked_rows if cfg != 5 else checked_rows * len(mots),
+                "full": args.full,
                 "input_buffers_rotated": rotate,
                 "bursts": len(burst_s),
                 "burst_steps": burst_steps,

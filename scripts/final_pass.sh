@@ -11,7 +11,7 @@ cd "$root"
 python -m pytest tests -m gpu -q 2>&1 | grep -E "passed|failed|error" > "$out/pytest.txt"
 python -c "import __graft_entry__ as g; g.smoke()" > "$out/smoke.txt" 2>&1
 for c in 2 3 4 5; do
-  python bench.py --config $c 2> "$out/bench_config$c.err" | tail -1 > "$out/bench_config$c.json"
+  python bench.py --full --config $c 2> "$out/bench_config$c.err" | tail -1 > "$out/bench_config$c.json"
 done
 cd /tmp && export TMPDIR=/tmp
 for c in 2 3 4 5; do

@@ -20,9 +20,9 @@ run "slots 6, ring 2" "" --slots 6 --score-buffers 2
 run "slots 8, ring 2" "" --slots 8 --score-buffers 2
 run "slots 8, ring 3" "" --slots 8 --score-buffers 3
 } | tee "$out"
-# ... and inside the FULL bench line (CPU baseline, TSV directories, extras: what the driver runs)
+# ... and inside the --full bench line (CPU baseline, TSV directories, extras)
 for cfg in "--slots 4 --score-buffers 2" "--slots 8 --score-buffers 2"; do
-  python3 bench.py --no-config45 $cfg 2>/dev/null | tail -1 | python3 -c "
+  python3 bench.py --full --no-config45 $cfg 2>/dev/null | tail -1 | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read()); r=d['roofline']; t=d.get('tail_ms') or {}
 print('FULL bench %-28s value %.4g  step %.2f us  kernel %.2f us  gap %.2f us  tail avg %.1f max %.1f us' % ('$cfg', d['value'], 1e3*d['ms_per_step'], 1e3*r['kernel_ms_avg'], 1e3*(d['ms_per_step']-r['kernel_ms_avg']), 1e3*t.get('avg',0), 1e3*t.get('max',0)))" | tee -a "$out"

@@ -748,7 +748,7 @@ def test_bench_distributed_path_on_one_gpu_with_reserved_cus():
     """The N > 1 bench path on the one GPU the test box has: --force-dist initialises RCCL with a one-rank group, every
     step issues the histogram all-reduce and the sized hit gather on the tail / gather streams beside a persistent score
     grid that leaves 16 CUs free (GRAFIMO_RESERVE_CUS=16, what bench.py sets for N > 1); the line must carry the group's
-    size, the tail timing with the collectives in it, and have passed its own oracle slice."""
+    size, the tail timing with the collectives in it, and have passed its own oracle slice (--full)."""
     import json
     import subprocess
     import sys
@@ -757,7 +757,7 @@ def test_bench_distributed_path_on_one_gpu_with_reserved_cus():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--force-dist", "--config", "3", "--rows", "8000000",
-                        "--steps", "12", "--warmup", "3", "--bursts", "2", "--no-cpu-baseline", "--no-e2e", "--no-extras"],
+                        "--steps", "12", "--warmup", "3", "--bursts", "2", "--full", "--no-cpu-baseline", "--no-e2e", "--no-extras"],
                        capture_output=True, text=True, env=env, timeout=800)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
     rec = json.loads([ln for ln in r.stdout.splitlines() if ln.strip().startswith("{")][-1])
@@ -798,10 +798,35 @@ def test_bench_steps_and_dumped_outputs(tmp_path):
 
 
 @pytest.mark.timeout(900)
+def test_plain_bench_run_leaves_the_side_blocks_out():
+    """The default line without --full: the headline fields and the score kernel's roofline (events that ride on the timed
+    steps) are there; the CPU baselines, the oracle slice and the other configs and paths, which take runs of their own,
+    are not."""
+    import json
+    import subprocess
+    import sys
+    from conftest import ROOT
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "6", "--warmup", "2"],
+                       capture_output=True, text=True, timeout=800)
+    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
+    rec = json.loads([ln for ln in r.stdout.splitlines() if ln.strip()][-1])
+    assert rec["metric"] == "scored haplotype k-mers/sec" and rec["unit"] == "k-mers/s" and rec["dtype"] == "int32"
+    assert rec["higher_is_better"] is True and rec["value"] > 0 and rec["ms_per_step"] > 0 and rec["steps"] == 6
+    cfg = rec["config"]
+    assert cfg["baseline_config"] == 2 and cfg["full"] is False and cfg["oracle_checked_rows"] == 0 and cfg["hits_last_step"] > 0
+    assert rec["roofline"]["kernel_launches_timed"] > 0
+    for name in ("cpu_baseline", "cpu_baseline_table", "e2e", "e2e_config2", "peak_measured", "roofline_noscore", "sustained",
+                 "roofline_config3", "roofline_config4", "roofline_config5", "extract", "extract_config4", "extract_config5",
+                 "strand_max", "pcie_inclusive", "product_paths"):
+        assert rec[name] is None, name
+    assert cfg["fused"] is None and rec["scaling_curve_point"]["kmers_per_s"] is None
+
+
+@pytest.mark.timeout(900)
 def test_bench_product_paths_block_under_a_process_group():
     """What `bench.py --gpus N` adds at N > 1 -- the fused graph path (a rank uploads its shard of the graph) and the streamed
-    scan under the run's process group -- driven with a one-rank RCCL group on the test box's one GPU: both blocks report rows
-    and rates, no error string."""
+    scan under the run's process group (--full) -- driven with a one-rank RCCL group on the test box's one GPU: both blocks
+    report rows and rates, no error string."""
     import json
     import subprocess
     import sys
@@ -810,7 +835,7 @@ def test_bench_product_paths_block_under_a_process_group():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--force-dist", "--config", "3", "--rows", "4000000",
-                        "--steps", "6", "--warmup", "2", "--bursts", "2", "--no-cpu-baseline", "--no-e2e"],
+                        "--steps", "6", "--warmup", "2", "--bursts", "2", "--full", "--no-cpu-baseline", "--no-e2e"],
                        capture_output=True, text=True, env=env, timeout=800)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
     rec = json.loads([ln for ln in r.stdout.splitlines() if ln.strip().startswith("{")][-1])
