@@ -104,6 +104,9 @@ def get_parser():
     p.add_argument("--haplotype-hits", action="store_true", dest="haplotype_hits",
                    help="also write grafimo_haplotype_hits[_MOTIF].tsv (printed with -f): per region, how many of the report's "
                         "rows each haplotype carries, one column per haplotype (graph routes only)")
+    p.add_argument("--haplotype-scores", action="store_true", dest="haplotype_scores",
+                   help="also write grafimo_haplotype_scores[_MOTIF].tsv (printed with -f): per region, each haplotype's best "
+                        "motif score whatever the threshold, beside the reference's (graph routes only)")
     p.add_argument("-j", "--cores", type=int, default=0, help="host threads for TSV ingest (0 = all)")
     p.add_argument("-o", "--out", default=DEFAULT_OUTDIR)
     p.add_argument("--verbose", action="store_true")
@@ -189,6 +192,8 @@ def main(argv=None):
                  "threshold (drop --qvalueT)")
     if a.haplotype_hits and a.sequences:
         sys.exit("ERROR: --haplotype-hits needs the graph (-g / -d with -b, or -l -v -b): the rows of -s carry no walks")
+    if a.haplotype_scores and a.sequences:
+        sys.exit("ERROR: --haplotype-scores needs the graph (-g / -d with -b, or -l -v -b): the rows of -s carry no walks")
     if not from_vg and (from_graph == bool(a.sequences) or (from_graph and not (a.linear_genome and a.vcf and a.bedfile))):
         sys.exit("ERROR: give -g XG / -d DIR with -b BED, or -s DIR, or all of -l FASTA -v VCF -b BED")
     if a.cores <= 0:
@@ -272,6 +277,22 @@ def main(argv=None):
                 continue
             path = write_haplotype_hits(hh, motif, len(motifs), wf)
             print(f"{hh.counts.shape[0]} x {hh.counts.shape[1]} haplotype hit counts written to {path}")
+    if a.haplotype_scores:
+        from .haplotype_scores import compute_haplotype_scores_many, print_haplotype_scores, write_haplotype_scores
+        if from_vg:
+            from .extract_regions import read_manifest
+            manifest = read_manifest(sequences_loc)
+            if manifest is None:
+                sys.exit("ERROR: --haplotype-scores needs the graph; scan_graph left TSV rows, which carry no walks")
+            tables = compute_haplotype_scores_many(motifs, manifest, None, a.debug, wf)
+        else:
+            tables = compute_haplotype_scores_many(motifs, graphs, region_lists, a.debug, wf)
+        for motif, hs in zip(motifs, tables):
+            if a.text_only:                            # -f: printed like the report, no file written
+                print_haplotype_scores(hs)
+                continue
+            path = write_haplotype_scores(hs, motif, len(motifs), wf)
+            print(f"{hs.best.shape[0]} x {hs.best.shape[1]} haplotype best scores written to {path}")
     if sequences_loc:
         import shutil
         shutil.rmtree(sequences_loc, ignore_errors=True)

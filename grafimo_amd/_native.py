@@ -133,6 +133,8 @@ PROTOTYPES = {
                                           c_void_p, c_void_p, c_void_p, c_void_p, P(c_i64), c_void_p]),
     "gfm_variant_effect_columns": (c_int, [c_void_p, c_i32, c_i32, ctypes.c_double, c_i32, c_i32, c_void_p, c_void_p, c_i64,
                                            ctypes.c_double, ctypes.c_uint32, P(c_i64)] + [c_void_p] * 10),
+    "gfm_graph_haplotype_scores": (c_int, [c_void_p, c_void_p, c_i32, c_i32, c_void_p, c_void_p, ctypes.c_uint32, c_void_p,
+                                           c_void_p, c_i32, c_i32, c_void_p]),
     "gfm_region_labels": (c_i64, [ctypes.c_char_p, c_void_p, c_void_p, c_i64, c_void_p, c_i64]),
     "gfm_vcf_open": (c_int, [ctypes.c_char_p, ctypes.c_char_p, c_int, c_int, P(c_void_p), P(c_i64), P(c_i32),
                              P(c_i64)]),

@@ -92,6 +92,37 @@ def _caller_rows(prep) -> List[np.ndarray]:
     return rows
 
 
+def _haplotype_set(prep, haplotype_names: Optional[Sequence[str]], what: str) -> Tuple[int, List[str]]:
+    """-> (H, column names) of the prepared call's graphs; ValueError when a graph carries no haplotypes or the graphs do not
+    share one haplotype set.  `what` names the result in the messages."""
+    for g in prep.graphs:
+        if g.index.alt_bits is None or int(g.index.n_haplotypes) <= 0:
+            raise ValueError(f"{g.index.chrom}: the graph carries no haplotypes (an XG without its GBWT, or a VCF without "
+                             f"samples): {what} needs them")
+    H = int(prep.graphs[0].index.n_haplotypes)
+    known = [g.index.sample_names for g in prep.graphs if getattr(g.index, "sample_names", None)]
+    if any(int(g.index.n_haplotypes) != H for g in prep.graphs) or any(k != known[0] for k in known):
+        raise ValueError("the chromosomes' graphs do not share one haplotype set (different samples or numbers of "
+                         "haplotypes): one matrix needs the same columns for all of them")
+    # (sample names only when every graph knows them: a graph from vg's files numbers its haplotypes instead)
+    names = haplotype_column_names(prep.graphs[0].index) if len(known) == len(prep.graphs) else [f"hap{k}" for k in range(H)]
+    if haplotype_names is not None:
+        names = [str(x) for x in haplotype_names]
+        if len(names) != H:
+            raise ValueError(f"{len(names)} haplotype names for {H} haplotypes")
+    return H, names
+
+
+def _matrix_rows(prep) -> Tuple[List[np.ndarray], np.ndarray]:
+    """-> (per graph handle the caller's rows of its regions (_caller_rows), the region names of the caller's rows)"""
+    rows = _caller_rows(prep)
+    R = int(sum(len(r) for r in rows))
+    region_names = np.empty(R, dtype=object)
+    for gi, r in enumerate(rows):
+        region_names[r] = prep.labels.take(prep.region_base[gi] + np.arange(len(r), dtype=np.int64))
+    return rows, region_names
+
+
 def compute_haplotype_hits_many(motifs: Sequence, graph, regions, debug: bool, args_obj, chrom_names=None,
                                 haplotype_names: Optional[Sequence[str]] = None,
                                 scratch_bytes: int = 0) -> List[HaplotypeHits]:
@@ -107,26 +138,9 @@ def compute_haplotype_hits_many(motifs: Sequence, graph, regions, debug: bool, a
         raise ValueError("no graph: a DeviceGraph / GraphIndex with its regions, lists of both, or a scan_graph manifest "
                          "(read_manifest gives None when scan_graph left TSV rows: GRAFIMO_SCAN_OUTPUT=manifest asks for one)")
     prep = _manifest_prep(graph) if isinstance(graph, dict) else _prepare_entries(graph, regions, chrom_names, None, False)
-    for g in prep.graphs:
-        if g.index.alt_bits is None or int(g.index.n_haplotypes) <= 0:
-            raise ValueError(f"{g.index.chrom}: the graph carries no haplotypes (an XG without its GBWT, or a VCF without "
-                             "samples): the per-haplotype hit matrix needs them")
-    H = int(prep.graphs[0].index.n_haplotypes)
-    known = [g.index.sample_names for g in prep.graphs if getattr(g.index, "sample_names", None)]
-    if any(int(g.index.n_haplotypes) != H for g in prep.graphs) or any(k != known[0] for k in known):
-        raise ValueError("the chromosomes' graphs do not share one haplotype set (different samples or numbers of "
-                         "haplotypes): one matrix needs the same columns for all of them")
-    # (sample names only when every graph knows them: a graph from vg's files numbers its haplotypes instead)
-    names = haplotype_column_names(prep.graphs[0].index) if len(known) == len(prep.graphs) else [f"hap{k}" for k in range(H)]
-    if haplotype_names is not None:
-        names = [str(x) for x in haplotype_names]
-        if len(names) != H:
-            raise ValueError(f"{len(names)} haplotype names for {H} haplotypes")
-    rows = _caller_rows(prep)
-    R = int(sum(len(r) for r in rows))
-    region_names = np.empty(R, dtype=object)
-    for gi, r in enumerate(rows):
-        region_names[r] = prep.labels.take(prep.region_base[gi] + np.arange(len(r), dtype=np.int64))
+    H, names = _haplotype_set(prep, haplotype_names, "the per-haplotype hit matrix")
+    rows, region_names = _matrix_rows(prep)
+    R = len(region_names)
     out: List[Optional[HaplotypeHits]] = [None] * len(motifs)
     by_width = {}
     for i, m in enumerate(motifs):

@@ -612,6 +612,24 @@ int gfm_variant_effect_columns(const double *h_ptable, int32_t table_len, int32_
                                uint8_t *o_found, double *o_score, double *o_pvalue, int64_t *o_start, int64_t *o_stop,
                                uint8_t *o_strand, uint8_t *o_kmers, uint8_t *o_effect);
 
+/* ------------------------------------------------------------------ per-haplotype best motif score (no threshold)
+ * For region r of the caller's list and haplotype h of the graph (its bitset order): the best of the report's threshold-1
+ * rows of r that h carries -- h is in the AND of the bitsets of the walk's allele constraints, the set whose size is
+ * haplotype_frequency; equivalently the k-mers of h's own sequence under the report's region rule, both strands unless
+ * GFM_GRAPH_FORWARD_ONLY.  No hit list is made.  Per motif m, d_keys[m] uint64 [n_regions][n_hap + 1], zeroed by the
+ * caller, receives the packed key of that row; column n_hap is the reference path (every site at its REF allele, carried
+ * or not).  Key = scaled score << 48 | (2^28 - 1 - (left - max(start, 0))) << 20 | (2^19 - 1 - (right - left)) << 1 | '+',
+ * with left / right the '+' row's start / stop: the largest key is the highest score, then the smallest left, then the
+ * smallest right, then '+' before '-'.  0: h has no row in r.  Motifs of ONE width (they share the call's run list).
+ * windows_per_run (0: 256, at most 1 024) and haplotypes_per_block (0: as few blocks of at most 4 096 as fit, else a
+ * multiple of 64) cut the work; the result does not depend on them.  *d_overflow (zeroed by the caller) = 1 if a window
+ * holds more than 2^24 walks: the matrix is not complete.  GFM_ERR_INVALID when the graph carries no haplotypes, a region
+ * (clipped to the chromosome) is longer than 2^28 - 1 bases, or a walk may span more than 2^19 - 1 bases.  Enqueue only
+ * (host work: the run list; the handle's calls are serialised as gfm_graph_score's are). */
+int gfm_graph_haplotype_scores(gfm_graph_t g, const gfm_motif_t *motifs, int32_t n_motifs, int32_t n_regions,
+                               const int64_t *h_starts, const int64_t *h_stops, uint32_t flags, uint64_t *const *d_keys,
+                               int32_t *d_overflow, int32_t windows_per_run, int32_t haplotypes_per_block, void *stream);
+
 /* Phased VCF (plain or gzip/bgzip) -> the site arrays of gfm_graph_create for one chromosome; host
  * threads parse the lines.  The reference hands the VCF to `vg construct` / `vg index -G`
  * (constructVG.py:332,394); here every ALT allele is taken apart: single-base substitutions (one site per

@@ -1,0 +1,60 @@
+"""Haplotype brute force for the per-haplotype best score matrix (grafimo_amd/haplotype_scores.py) -- TEST INFRASTRUCTURE ONLY.
+
+Every haplotype is spelled from the reference and the alleles its bitsets give it (variant_bruteforce.spell); every window
+of W consecutive bases of it is a row under the report's region rule (start -- the first base's coordinate, + 1 if that
+base was inserted -- in [S, E), stop -- the last base's coordinate + 1 -- <= E), scored on both strands unless forward_only
+(the '-' row is the reverse complement).  best(r, h) is the row with the largest key: the highest integer score, then the
+smallest start, the smallest stop, '+' before '-' -- the order haplotype_scores.pack_key encodes.  The reference column
+spells the index with every ALT bitset cleared.  No walk enumeration and no kernel is involved.
+"""
+import copy
+import os
+import sys
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from variant_bruteforce import int_score, revcomp, spell  # noqa: E402
+from grafimo_amd.haplotype_scores import pack_key  # noqa: E402
+
+
+def _best_keys(seq, coord, ins, regions, W, L, score, forward_only):
+    best = [None] * len(regions)                      # (score, -start, -stop, '+') of the best row: larger is better
+    for o in range(0, len(seq) - W + 1):
+        start = coord[o] + (1 if ins[o] else 0)
+        stop = coord[o + W - 1] + 1
+        kmer = bytes(seq[o:o + W])
+        strands = [(score(kmer), 1)] + ([] if forward_only else [(score(revcomp(kmer)), 0)])
+        for r, (S, E) in enumerate(regions):
+            if not (max(S, 0) <= start < min(E, L) and stop <= min(E, L)):
+                continue
+            for s, plus in strands:
+                t = (s, -start, -stop, plus)
+                if best[r] is None or t > best[r]:
+                    best[r] = t
+    return [0 if b is None else int(pack_key(b[0], -b[1], -b[2], b[3], max(S, 0))) for b, (S, _) in zip(best, regions)]
+
+
+def haplotype_score_keys(idx, regions, W: int, sm: np.ndarray, min_val: int, forward_only: bool = False) -> np.ndarray:
+    """-> keys uint64 [R, H + 1] (0: no row), column H the reference path"""
+    sm = np.asarray(sm, dtype=np.int64)
+    H = int(idx.n_haplotypes) if idx.alt_bits is not None else 0
+    L = len(idx.ref)
+    memo = {}
+
+    def score(k: bytes) -> int:
+        s = memo.get(k)
+        if s is None:
+            s = memo[k] = int_score(k, sm, min_val)
+        return s
+
+    out = np.zeros((len(regions), H + 1), dtype=np.uint64)
+    for h in range(H):
+        seq, coord, ins, _, _ = spell(idx, h)
+        out[:, h] = _best_keys(seq, coord, ins, regions, W, L, score, forward_only)
+    ref = copy.copy(idx)
+    ref.alt_bits = None                                  # no haplotype carries an ALT allele: the reference path
+    seq, coord, ins, _, _ = spell(ref, 0)
+    out[:, H] = _best_keys(seq, coord, ins, regions, W, L, score, forward_only)
+    return out

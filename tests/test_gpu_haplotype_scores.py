@@ -1,0 +1,276 @@
+"""Per-haplotype best score matrix on the GPU (gfm_graph_haplotype_scores -> grafimo_amd.haplotype_scores) against the score
+brute force of tests/haplotype_score_bruteforce.py, the threshold-1 route through the hit list, the two tutorial routes and
+the CLI."""
+import contextlib
+import io
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pandas as pd
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+from extract_helpers import make_consistent_graph_files, motif_as_oracle_dict  # noqa: E402
+from haplotype_score_bruteforce import haplotype_score_keys  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+GOLD = os.path.join(ROOT, "tests", "golden", "ref_data")
+
+
+class _Args:
+    def __init__(self, threshold=1e-4, no_reverse=False, recomb=False, qvalue_t=False, no_qvalue=True):
+        self.threshold, self.noreverse, self.recomb = threshold, no_reverse, recomb
+        self.noqvalue, self.qvalueT = no_qvalue, qvalue_t
+
+
+def _motif(W, seed=0):
+    from grafimo_amd import synth
+    rec = synth.synthetic_motif(W, np.random.default_rng(2900 + 13 * W + seed), np.array([0.3, 0.2, 0.2, 0.3]))
+    return synth.motif_object(rec, f"SYN{W}")
+
+
+def _ctcf():
+    from grafimo_amd.motif_ops import build_motif_meme_host
+    return build_motif_meme_host(os.path.join(GOLD, "MA0139.1.meme"), "unfrm_dst", 0.1, False)[0]
+
+
+def _check_bruteforce(hs, idx, regions, motif, forward_only):
+    """every cell against the brute force: the key bit for bit, and the fields made from it"""
+    from grafimo_amd.haplotype_scores import unpack_keys
+    od = motif_as_oracle_dict(motif)
+    W = od["width"]
+    exp = haplotype_score_keys(idx, regions, W, od["score_matrix"], od["min_val"], forward_only=forward_only)
+    assert hs.keys.shape == exp.shape
+    assert (hs.keys == exp).all(), np.argwhere(hs.keys != exp)[:5]
+    base = np.array([max(S, 0) for S, _ in regions], dtype=np.int64)[:, None]
+    best, left, right, plus = unpack_keys(exp, base)
+    ptab = np.cumsum(od["pmf"][::-1])[::-1]
+    some = best >= 0
+    full_best = np.concatenate([hs.best, hs.reference_best[:, None]], axis=1)
+    assert (full_best == best).all()
+    score = np.concatenate([hs.best_score, hs.reference_score[:, None]], axis=1)
+    assert np.array_equal(score, np.where(some, best / od["scale"] + W * od["offset"], np.nan), equal_nan=True)
+    pv = np.concatenate([hs.best_pvalue, hs.reference_pvalue[:, None]], axis=1)
+    assert np.allclose(pv, np.where(some, ptab[np.where(some, best, 0)], np.nan), rtol=1e-12, atol=0, equal_nan=True)
+    start = np.concatenate([hs.start, hs.reference_start[:, None]], axis=1)
+    stop = np.concatenate([hs.stop, hs.reference_stop[:, None]], axis=1)
+    strand = np.concatenate([hs.strand, hs.reference_strand[:, None]], axis=1)
+    assert (start == np.where(some, np.where(plus, left, right), -1)).all()
+    assert (stop == np.where(some, np.where(plus, right, left), -1)).all()
+    assert (strand == np.where(some, np.where(plus, "+", "-"), "")).all()
+    if forward_only:
+        assert not (strand == "-").any()
+    return best
+
+
+@pytest.mark.parametrize("seed,W,no_reverse", [(1, 5, False), (2, 8, True), (3, 12, False), (4, 19, True), (5, 30, False),
+                                               (6, 64, False)])
+def test_bruteforce_parity(tmp_path, seed, W, no_reverse):
+    from grafimo_amd.extract_regions import GraphIndex
+    from grafimo_amd.haplotype_scores import compute_haplotype_scores
+    fa, vcf = make_consistent_graph_files(str(tmp_path), length=400, n_samples=12, seed=seed, kinds="sidmDOc")
+    idx = GraphIndex.from_fasta_vcf(fa, vcf, "c")
+    p = idx.pos
+    # overlapping, the whole chromosome, shorter than W, starting / ending on a site
+    regions = [(0, int(p[len(p) // 3]) + 1), (int(p[len(p) // 3]) - 2, int(p[2 * len(p) // 3])), (int(p[-3]), 400), (0, 400),
+               (3, 4), (int(p[len(p) // 2]), int(p[len(p) // 2]) + W + 3), (-10, 500)]
+    motif = _motif(W, seed)
+    hs = compute_haplotype_scores(motif, idx, regions, False, _Args(no_reverse=no_reverse))
+    best = _check_bruteforce(hs, idx, regions, motif, no_reverse)
+    assert (best[3] >= 0).all() and (best[4] == -1).all()
+    assert hs.haplotype_names == [f"s{k}|{j}" for k in range(12) for j in (1, 2)]
+    assert hs.region_names.tolist() == [f"c:{S}-{E}" for S, E in regions]
+
+
+@pytest.mark.parametrize("seed,W,no_reverse", [(11, 8, False), (12, 19, True)])
+def test_equals_threshold_one_hit_route(tmp_path, seed, W, no_reverse):
+    from grafimo_amd.extract_regions import GraphIndex
+    from grafimo_amd.haplotype_hits import compute_haplotype_hits
+    from grafimo_amd.haplotype_scores import compute_haplotype_scores
+    fa, vcf = make_consistent_graph_files(str(tmp_path), length=500, n_samples=20, seed=seed, kinds="sidmDOc")
+    idx = GraphIndex.from_fasta_vcf(fa, vcf, "c")
+    regions = [(0, 250), (200, 500), (100, 101), (0, 500)]
+    motif = _motif(W, seed)
+    args = _Args(threshold=1.0, no_reverse=no_reverse)
+    hs = compute_haplotype_scores(motif, idx, regions, False, args)
+    hh = compute_haplotype_hits(motif, idx, regions, False, args)
+    assert (hs.best == hh.best).all()
+    assert np.array_equal(hs.best_score, hh.best_score, equal_nan=True)
+
+
+def test_equals_threshold_one_hit_route_at_bench_density():
+    """synth.make_graph_index at bench density: 5 096 haplotypes, two blocks of the default launch"""
+    from grafimo_amd import synth
+    from grafimo_amd.extract_regions import DeviceGraph
+    from grafimo_amd.haplotype_hits import compute_haplotype_hits
+    from grafimo_amd.haplotype_scores import compute_haplotype_scores
+    idx, regions = synth.make_graph_index(2000, 19)
+    assert idx.n_haplotypes == 5096
+    g = DeviceGraph(idx)
+    motif = _ctcf()
+    args = _Args(threshold=1.0)
+    hs = compute_haplotype_scores(motif, g, regions, False, args)
+    hh = compute_haplotype_hits(motif, g, regions, False, args)
+    assert (hs.best == hh.best).all()
+    assert (hs.best >= 0).all()
+    g.close()
+
+
+def _dense_window_graph(n_hap, seed=3):
+    """one window of 19 bases over 18 biallelic sites (2^18 walks), haplotypes with random alleles"""
+    from grafimo_amd.extract_regions import GraphIndex
+    rng = np.random.default_rng(seed)
+    ref = np.frombuffer(b"ACGT", dtype=np.uint8)[rng.integers(0, 4, 400)]
+    pos = np.arange(100, 118, dtype=np.int32)
+    alt = np.zeros((len(pos), 3), np.uint8)
+    alt[:, 0] = np.where(ref[pos] == ord("A"), ord("C"), ord("A"))
+    hw = (n_hap + 63) // 64
+    carry = rng.random((len(pos), n_hap)) < 0.4
+    bits = np.zeros((len(pos), 3, hw), np.uint64)
+    for h in range(n_hap):
+        bits[:, 0, h >> 6] |= carry[:, h].astype(np.uint64) << np.uint64(h & 63)
+    return GraphIndex("c", ref, pos, np.ones(len(pos), np.uint8), alt, bits, n_hap)
+
+
+def test_beyond_the_report_hit_limit(monkeypatch):
+    """threshold-1 through the hit list is refused at GRAFIMO_MAX_HITS; the matrix needs no hit list"""
+    from grafimo_amd import _native as nv
+    from grafimo_amd import extract_regions as xr
+    from grafimo_amd.haplotype_hits import compute_haplotype_hits
+    from grafimo_amd.haplotype_scores import compute_haplotype_scores
+    idx = _dense_window_graph(203)
+    regions = [(90, 130), (0, 400)]
+    motif = _ctcf()
+    monkeypatch.setattr(xr, "MAX_HITS", 100_000)
+    with contextlib.redirect_stdout(io.StringIO()):
+        with pytest.raises(nv.NativeError) as e:
+            compute_haplotype_hits(motif, idx, regions, False, _Args(threshold=1.0))
+    assert e.value.code == nv.GFM_ERR_OVERFLOW and "GRAFIMO_MAX_HITS" in str(e.value)
+    hs = compute_haplotype_scores(motif, idx, regions, False, _Args(threshold=1.0))
+    assert (_check_bruteforce(hs, idx, regions, motif, False) >= 0).all()
+
+
+def test_overflow_is_an_error():
+    from grafimo_amd.extract_regions import GraphIndex
+    from grafimo_amd.haplotype_scores import compute_haplotype_scores
+    ref = np.frombuffer(b"ACGT" * 25, dtype=np.uint8)
+    pos = np.arange(20, 33, dtype=np.int32)          # 13 sites of 3 ALTs in one window of 19: 4^13 walks
+    alt = np.array([[c for c in b"ACGT" if c != ref[q]] for q in pos], dtype=np.uint8)
+    idx = GraphIndex("c", ref, pos, np.full(13, 3, np.uint8), alt, np.ones((13, 3, 1), np.uint64), 2)
+    # (only windows that see all 13 sites: a window of exactly 4^12 = 2^24 walks would be replayed)
+    with pytest.raises(OverflowError):
+        compute_haplotype_scores(_motif(19), idx, [(14, 39)], False, _Args())
+
+
+def test_decomposition_invariance(tmp_path):
+    """runs of 1 and 3 windows, blocks of 64 haplotypes, H = 150: the keys bit for bit"""
+    from grafimo_amd.extract_regions import DeviceGraph, GraphIndex
+    from grafimo_amd.haplotype_scores import compute_haplotype_scores
+    fa, vcf = make_consistent_graph_files(str(tmp_path), length=600, n_samples=75, seed=31, kinds="sidmDOc")
+    idx = GraphIndex.from_fasta_vcf(fa, vcf, "c")
+    assert idx.n_haplotypes == 150
+    g = DeviceGraph(idx)
+    regions = [(0, 300), (250, 600), (0, 600), (40, 45)]
+    motif = _motif(8, 3)
+    ref = compute_haplotype_scores(motif, g, regions, False, _Args())
+    _check_bruteforce(ref, idx, regions, motif, False)
+    for wpr, hpb in ((1, 64), (3, 64), (3, 0), (0, 128), (1024, 192)):
+        got = compute_haplotype_scores(motif, g, regions, False, _Args(), windows_per_run=wpr, haplotypes_per_block=hpb)
+        assert (got.keys == ref.keys).all(), (wpr, hpb)
+    g.close()
+
+
+def test_flags_many_and_refusal(tmp_path):
+    from grafimo_amd.extract_regions import GraphIndex
+    from grafimo_amd.haplotype_scores import compute_haplotype_scores, compute_haplotype_scores_many
+    fa, vcf = make_consistent_graph_files(str(tmp_path), length=500, n_samples=12, seed=29, kinds="sidmDOc")
+    idx = GraphIndex.from_fasta_vcf(fa, vcf, "c")
+    regions = [(0, 300), (200, 500)]
+    m = _motif(8, 1)
+    ref = compute_haplotype_scores(m, idx, regions, False, _Args())
+    for args in (_Args(recomb=True), _Args(threshold=1e-8), _Args(threshold=0.5, qvalue_t=True, no_qvalue=False)):
+        assert (compute_haplotype_scores(m, idx, regions, False, args).keys == ref.keys).all()
+    for motifs in ([_motif(8, 1), _motif(8, 2), _motif(8, 3)], [_motif(8, 1), _motif(12, 2), _motif(8, 3), _motif(12, 4)]):
+        many = compute_haplotype_scores_many(motifs, idx, regions, False, _Args())
+        for mo, t in zip(motifs, many):
+            one = compute_haplotype_scores(mo, idx, regions, False, _Args())
+            assert t.motif_id == mo.motif_id and (t.keys == one.keys).all()
+    # entries that share one graph: rows in the caller's entry order
+    split = compute_haplotype_scores(m, [idx, idx], [[regions[1]], [regions[0]]], False, _Args(), chrom_names=["c", "c"])
+    assert (split.keys == ref.keys[::-1]).all() and split.region_names.tolist() == ref.region_names.tolist()[::-1]
+    bare = GraphIndex("c", np.frombuffer(b"ACGT" * 25, dtype=np.uint8), np.array([10], np.int32), np.array([1], np.uint8),
+                      np.array([[ord("A"), 0, 0]], np.uint8), None, 0)
+    with pytest.raises(ValueError, match="carries no haplotypes"):
+        compute_haplotype_scores(m, bare, [(0, 100)], False, _Args())
+
+
+@pytest.fixture()
+def mygenome(tmp_path, monkeypatch):
+    import shutil
+    g = tmp_path / "data" / "mygenome"
+    shutil.copytree(os.path.join(GOLD, "mygenome"), g)     # (scan_graph saves x.gfmidx.npz beside x.xg)
+    monkeypatch.setenv("GRAFIMO_INDEX_CACHE", str(tmp_path / "cache"))
+    monkeypatch.delenv("GRAFIMO_SCAN_OUTPUT", raising=False)
+    return str(g)
+
+
+def test_manifest_route_equals_fasta_vcf_route(tmp_path, mygenome, monkeypatch):
+    import shutil
+    from grafimo_amd.extract_regions import DeviceGraph, GraphIndex, read_bed_regions, read_manifest, scan_graph
+    from grafimo_amd.haplotype_scores import compute_haplotype_scores
+    from grafimo_amd.motif_ops import get_motif_pwm
+    from grafimo_amd.workflow import Findmotif
+    bed = os.path.join(tmp_path, "x.bed")
+    with open(os.path.join(GOLD, "regions.bed")) as src, open(bed, "w") as dst:
+        dst.writelines(line for line in src if line.startswith("chrx\t"))
+    wf = Findmotif(graph_genome_dir=mygenome, bedfile=bed, cores=2, threshold=0.05)
+    motif = get_motif_pwm(os.path.join(GOLD, "example.meme"), wf, 2, True, pvalue_matrix=False)[0]
+    monkeypatch.setenv("GRAFIMO_SCAN_OUTPUT", "manifest")
+    with contextlib.redirect_stdout(io.StringIO()):
+        loc = scan_graph({motif.width}, wf, True)
+    try:
+        man = read_manifest(loc)
+        assert man is not None
+        a = compute_haplotype_scores(motif, man, None, False, _Args())
+        idx = GraphIndex.from_fasta_vcf(os.path.join(GOLD, "xy.fa"), os.path.join(GOLD, "xy2.vcf.gz"), "x")
+        b = compute_haplotype_scores(motif, DeviceGraph(idx), read_bed_regions(bed)["chrx"], False, _Args())
+        assert a.haplotype_names == ["hap0", "hap1"] and b.haplotype_names == ["1|1", "1|2"]
+        assert a.region_names.tolist() == b.region_names.tolist()
+        assert (a.keys == b.keys).all() and (a.best >= 0).any()
+    finally:
+        shutil.rmtree(loc, ignore_errors=True)
+
+
+def test_cli_writes_matrix_and_leaves_report_alone(tmp_path):
+    base = [sys.executable, "-m", "grafimo_amd", "-m", os.path.join(GOLD, "MA0139.1.meme"), "-l", os.path.join(GOLD, "xy.fa"),
+            "-v", os.path.join(GOLD, "xy2.vcf.gz"), "-b", os.path.join(GOLD, "regions.bed"), "-t", "0.05"]
+    a, b = str(tmp_path / "a"), str(tmp_path / "b")
+    env = dict(os.environ, PYTHONPATH=ROOT)
+    subprocess.run(base + ["-o", a], check=True, cwd=str(tmp_path), env=env, timeout=600)
+    r = subprocess.run(base + ["-o", b, "--haplotype-scores"], check=True, cwd=str(tmp_path), env=env, timeout=600,
+                       capture_output=True, text=True)
+    fa, fb = sorted(os.listdir(a)), sorted(os.listdir(b))
+    assert fb == sorted(fa + ["grafimo_haplotype_scores.tsv"])
+    for f in fa:
+        assert open(os.path.join(a, f), "rb").read() == open(os.path.join(b, f), "rb").read(), f
+    assert "haplotype best scores written to" in r.stdout
+    path = os.path.join(b, "grafimo_haplotype_scores.tsv")
+    t = pd.read_csv(path, sep="\t")
+    assert list(t.columns) == ["motif_id", "motif_alt_id", "sequence_name", "reference", "1|1", "1|2"]
+    from grafimo_amd.extract_regions import GraphIndex, read_bed_regions
+    from grafimo_amd.haplotype_scores import compute_haplotype_scores_many
+    motif = _ctcf()
+    bed = read_bed_regions(os.path.join(GOLD, "regions.bed"))
+    graphs = [GraphIndex.from_fasta_vcf(os.path.join(GOLD, "xy.fa"), os.path.join(GOLD, "xy2.vcf.gz"), c[3:]) for c in bed]
+    hs = compute_haplotype_scores_many([motif], graphs, [bed[c] for c in bed], False, _Args(threshold=0.05))[0]
+    assert open(path).read() == hs.to_frame().to_csv(sep="\t", index=False, lineterminator="\n")
+    pd.testing.assert_frame_equal(t, hs.to_frame(), check_dtype=False)
+    r = subprocess.run(base + ["-o", str(tmp_path / "c"), "-f", "--haplotype-scores"], check=True, cwd=str(tmp_path), env=env,
+                       timeout=600, capture_output=True, text=True)
+    assert "motif_id\tmotif_alt_id\tsequence_name\treference\t1|1\t1|2\n" in r.stdout
+    assert not os.path.exists(tmp_path / "c" / "grafimo_haplotype_scores.tsv")
