@@ -108,6 +108,8 @@ PROTOTYPES = {
     "gfm_scan_table": (c_void_p, [c_void_p]),
     "gfm_scan_close": (None, [c_void_p]),
     "gfm_scan_release_buffers": (None, []),
+    "gfm_graph_validate": (c_int, [c_void_p, c_i64, c_i32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                   c_void_p, c_i64, c_i32]),
     "gfm_graph_create": (c_int, [c_void_p, c_i64, c_i32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                  c_void_p, c_i64, c_void_p, c_i32, P(c_void_p)]),
     "gfm_graph_destroy": (None, [c_void_p]),

@@ -1322,36 +1322,25 @@ struct gfm_graph {
     }
 };
 
-GFM_API int gfm_graph_create(const uint8_t *h_ref, int64_t ref_len, int32_t n_sites, const int32_t *h_pos,
+// the arrays' rules, on the host before anything touches a device (gfm_graph_create, gfm_graph_validate)
+static int graph_check_sites(const uint8_t *h_ref, int64_t ref_len, int32_t n_sites, const int32_t *h_pos,
                              const uint8_t *h_n_alts, const uint8_t *h_alt_bases, const int32_t *h_del_len,
                              const int32_t *h_ins_len, const int32_t *h_ins_off, const uint8_t *h_ins_bases,
-                             int64_t ins_bytes, const uint64_t *h_alt_bits, int32_t n_haplotypes, gfm_graph_t *out)
+                             int64_t ins_bytes, int32_t n_haplotypes)
 {
-    if (!out) return gfail(GFM_ERR_INVALID, "NULL output handle");
-    *out = nullptr;
     if (!h_ref || ref_len <= 0 || n_sites < 0 || n_haplotypes < 0)
         return gfail(GFM_ERR_INVALID, "bad reference / site count");
     if (n_sites && (!h_pos || !h_n_alts || !h_alt_bases)) return gfail(GFM_ERR_INVALID, "NULL site arrays");
-    std::vector<int> del_len((size_t)n_sites, 0), prev_del((size_t)n_sites + 1, -1), ins_len((size_t)n_sites, 0),
-        ins_off((size_t)n_sites, 0);
-    std::vector<long long> max_reach((size_t)n_sites + 1, -1);
-    int n_dels = 0, n_ins = 0;
-    long long max_del_len = 0;
-    long long deleted_until = -1;        // last reference position removed by an earlier deletion
-    auto kind_of = [&](int i) { return del_len[(size_t)i] > 0 ? 2 : (ins_len[(size_t)i] > 0 ? 1 : 0); };
+    auto kind_of = [&](int i) { return (h_del_len && h_del_len[i] > 0) ? 2 : ((h_ins_len && h_ins_len[i] > 0) ? 1 : 0); };
     for (int i = 0; i < n_sites; ++i) {
         const int dl = h_del_len ? h_del_len[i] : 0;
         const int il = h_ins_len ? h_ins_len[i] : 0;
         if (dl < 0 || il < 0 || (dl > 0 && il > 0))
             return gfail(GFM_ERR_INVALID, "a site is a substitution, an insertion or a deletion (site " + std::to_string(i) + ")");
-        del_len[(size_t)i] = dl;
-        ins_len[(size_t)i] = il;
         if (il > 0) {
             const long long off = h_ins_off ? h_ins_off[i] : -1;
             if (!h_ins_bases || off < 0 || off + il > ins_bytes)
                 return gfail(GFM_ERR_INVALID, "inserted bases outside the pool (site " + std::to_string(i) + ")");
-            ins_off[(size_t)i] = (int)off;
-            ++n_ins;
         }
         // same position: the substitution site first, then insertions, then the deletions
         const bool tie_ok = i && h_pos[i] == h_pos[i - 1] &&
@@ -1365,6 +1354,44 @@ GFM_API int gfm_graph_create(const uint8_t *h_ref, int64_t ref_len, int32_t n_si
         if ((dl > 0 || il > 0) && h_n_alts[i] != 1)
             return gfail(GFM_ERR_INVALID, "an insertion / a deletion has one alternate allele (site " +
                                               std::to_string(i) + ")");
+    }
+    return GFM_OK;
+}
+
+GFM_API int gfm_graph_validate(const uint8_t *h_ref, int64_t ref_len, int32_t n_sites, const int32_t *h_pos,
+                               const uint8_t *h_n_alts, const uint8_t *h_alt_bases, const int32_t *h_del_len,
+                               const int32_t *h_ins_len, const int32_t *h_ins_off, const uint8_t *h_ins_bases,
+                               int64_t ins_bytes, int32_t n_haplotypes)
+{
+    return graph_check_sites(h_ref, ref_len, n_sites, h_pos, h_n_alts, h_alt_bases, h_del_len, h_ins_len, h_ins_off,
+                             h_ins_bases, ins_bytes, n_haplotypes);
+}
+
+GFM_API int gfm_graph_create(const uint8_t *h_ref, int64_t ref_len, int32_t n_sites, const int32_t *h_pos,
+                             const uint8_t *h_n_alts, const uint8_t *h_alt_bases, const int32_t *h_del_len,
+                             const int32_t *h_ins_len, const int32_t *h_ins_off, const uint8_t *h_ins_bases,
+                             int64_t ins_bytes, const uint64_t *h_alt_bits, int32_t n_haplotypes, gfm_graph_t *out)
+{
+    if (!out) return gfail(GFM_ERR_INVALID, "NULL output handle");
+    *out = nullptr;
+    if (const int rc = graph_check_sites(h_ref, ref_len, n_sites, h_pos, h_n_alts, h_alt_bases, h_del_len, h_ins_len,
+                                         h_ins_off, h_ins_bases, ins_bytes, n_haplotypes))
+        return rc;
+    std::vector<int> del_len((size_t)n_sites, 0), prev_del((size_t)n_sites + 1, -1), ins_len((size_t)n_sites, 0),
+        ins_off((size_t)n_sites, 0);
+    std::vector<long long> max_reach((size_t)n_sites + 1, -1);
+    int n_dels = 0, n_ins = 0;
+    long long max_del_len = 0;
+    long long deleted_until = -1;        // last reference position removed by an earlier deletion
+    for (int i = 0; i < n_sites; ++i) {
+        const int dl = h_del_len ? h_del_len[i] : 0;
+        const int il = h_ins_len ? h_ins_len[i] : 0;
+        del_len[(size_t)i] = dl;
+        ins_len[(size_t)i] = il;
+        if (il > 0) {
+            ins_off[(size_t)i] = h_ins_off[i];
+            ++n_ins;
+        }
         if (dl > 0) {
             deleted_until = std::max(deleted_until, (long long)h_pos[i] + dl);
             ++n_dels;

@@ -45,6 +45,9 @@ COLUMNS = ["motif_id", "motif_alt_id", "sequence_name", "position", "ref", "alt"
            "ref_score", "ref_pvalue", "ref_start", "ref_stop", "ref_strand", "ref_sequence",
            "alt_score", "alt_pvalue", "alt_start", "alt_stop", "alt_strand", "alt_sequence", "delta_score", "effect"]
 _STRANDS = np.array(["+", "-"], dtype=object)
+# records of _scan's first call per motif (0: its guess from the sites the regions reach); tests set it small to take the
+# path where the call is made again with the count
+_FIRST_REC_CAPACITY = 0
 
 
 def _entries(graph, regions, chrom_names):
@@ -161,7 +164,7 @@ def _scan(dg, starts, stops, dms, forward_only: bool, recomb: bool):
     pos = np.asarray(dg.index.pos)
     reach = int(dg.index.del_len.max(initial=0)) + int(dms[0].width) + 1
     near = int((np.searchsorted(pos, stops, side="right") - np.searchsorted(pos, starts - reach)).clip(min=0).sum())
-    cap = 2 * 4 * near + 1024
+    cap = _FIRST_REC_CAPACITY if _FIRST_REC_CAPACITY > 0 else 2 * 4 * near + 1024
     flags = (nv.GFM_GRAPH_FORWARD_ONLY if forward_only else 0) | (nv.GFM_VARIANT_KEEP_ZERO_FREQ if recomb else 0)
     vp = ctypes.c_void_p
     with torch.cuda.device(dg.device):

@@ -394,6 +394,12 @@ void gfm_scan_release_buffers(void);
  *   allele is the reference's, also when a deletion is taken), d_region (index into the plan's
  *   regions), d_walk (walk index inside its window).  Enqueue only. */
 typedef struct gfm_graph *gfm_graph_t;
+/* gfm_graph_validate: the checks gfm_graph_create makes of its arguments (minus h_alt_bits and out), on the host only:
+ * GFM_OK or GFM_ERR_INVALID with the reason.  Touches no device. */
+int gfm_graph_validate(const uint8_t *h_ref, int64_t ref_len, int32_t n_sites, const int32_t *h_pos,
+                       const uint8_t *h_n_alts, const uint8_t *h_alt_bases, const int32_t *h_del_len,
+                       const int32_t *h_ins_len, const int32_t *h_ins_off, const uint8_t *h_ins_bases,
+                       int64_t ins_bytes, int32_t n_haplotypes);
 int gfm_graph_create(const uint8_t *h_ref, int64_t ref_len, int32_t n_sites, const int32_t *h_pos,
                      const uint8_t *h_n_alts, const uint8_t *h_alt_bases, const int32_t *h_del_len,
                      const int32_t *h_ins_len, const int32_t *h_ins_off, const uint8_t *h_ins_bases,

@@ -9,26 +9,29 @@ at or above `cutoff`.  counts[r, h] = the rows of haplotype h in region r that c
 """
 import numpy as np
 
-from variant_bruteforce import int_score, revcomp, spell
+from variant_bruteforce import haplotype_classes, int_score, revcomp, spell
 
 
-def haplotype_matrix(idx, regions, W: int, sm: np.ndarray, min_val: int, cutoff: int, forward_only: bool = False):
-    """-> (counts int64 [R, H], best int64 [R, H])"""
+def haplotype_matrix(idx, regions, W: int, sm: np.ndarray, min_val: int, cutoff: int, forward_only: bool = False,
+                     memo: bool = False):
+    """-> (counts int64 [R, H], best int64 [R, H]).  `memo`: one haplotype per class of haplotype_classes, its columns
+    copied to the class (the same result)."""
     sm = np.asarray(sm, dtype=np.int64)
     H = int(idx.n_haplotypes) if idx.alt_bits is not None else 0
     L = len(idx.ref)
     R = len(regions)
     counts = np.zeros((R, H), dtype=np.int64)
     best = np.full((R, H), -1, dtype=np.int64)
-    memo = {}
+    cache = {}
 
     def score(k: bytes) -> int:
-        s = memo.get(k)
+        s = cache.get(k)
         if s is None:
-            s = memo[k] = int_score(k, sm, min_val)
+            s = cache[k] = int_score(k, sm, min_val)
         return s
 
-    for h in range(H):
+    first, cls = haplotype_classes(idx) if memo else (np.arange(H), np.arange(H))
+    for h in first.tolist():
         seq, coord, ins, _, _ = spell(idx, h)
         for o in range(0, len(seq) - W + 1):
             start = coord[o] + (1 if ins[o] else 0)
@@ -42,7 +45,7 @@ def haplotype_matrix(idx, regions, W: int, sm: np.ndarray, min_val: int, cutoff:
                     if s >= cutoff:
                         counts[r, h] += 1
                         best[r, h] = max(best[r, h], s)
-    return counts, best
+    return counts[:, first[cls]], best[:, first[cls]]
 
 
 def integer_cutoff(ptable: np.ndarray, threshold: float) -> int:

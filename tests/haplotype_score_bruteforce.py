@@ -15,7 +15,7 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-from variant_bruteforce import int_score, revcomp, spell  # noqa: E402
+from variant_bruteforce import haplotype_classes, int_score, revcomp, spell  # noqa: E402
 from grafimo_amd.haplotype_scores import pack_key  # noqa: E402
 
 
@@ -36,23 +36,27 @@ def _best_keys(seq, coord, ins, regions, W, L, score, forward_only):
     return [0 if b is None else int(pack_key(b[0], -b[1], -b[2], b[3], max(S, 0))) for b, (S, _) in zip(best, regions)]
 
 
-def haplotype_score_keys(idx, regions, W: int, sm: np.ndarray, min_val: int, forward_only: bool = False) -> np.ndarray:
-    """-> keys uint64 [R, H + 1] (0: no row), column H the reference path"""
+def haplotype_score_keys(idx, regions, W: int, sm: np.ndarray, min_val: int, forward_only: bool = False,
+                         memo: bool = False) -> np.ndarray:
+    """-> keys uint64 [R, H + 1] (0: no row), column H the reference path.  `memo`: one haplotype per class of
+    haplotype_classes, its column copied to the class (the same result)."""
     sm = np.asarray(sm, dtype=np.int64)
     H = int(idx.n_haplotypes) if idx.alt_bits is not None else 0
     L = len(idx.ref)
-    memo = {}
+    cache = {}
 
     def score(k: bytes) -> int:
-        s = memo.get(k)
+        s = cache.get(k)
         if s is None:
-            s = memo[k] = int_score(k, sm, min_val)
+            s = cache[k] = int_score(k, sm, min_val)
         return s
 
     out = np.zeros((len(regions), H + 1), dtype=np.uint64)
-    for h in range(H):
+    first, cls = haplotype_classes(idx) if memo else (np.arange(H), np.arange(H))
+    for h in first.tolist():
         seq, coord, ins, _, _ = spell(idx, h)
         out[:, h] = _best_keys(seq, coord, ins, regions, W, L, score, forward_only)
+    out[:, :H] = out[:, first[cls]]
     ref = copy.copy(idx)
     ref.alt_bits = None                                  # no haplotype carries an ALT allele: the reference path
     seq, coord, ins, _, _ = spell(ref, 0)

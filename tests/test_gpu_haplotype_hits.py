@@ -12,8 +12,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-from extract_helpers import make_consistent_graph_files, motif_as_oracle_dict  # noqa: E402
-from haplotype_bruteforce import haplotype_matrix, integer_cutoff  # noqa: E402
+from extract_helpers import make_consistent_graph_files  # noqa: E402
+from graph_table_checks import check_haplotype_hits as _check_bruteforce  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(ROOT, "tests", "golden", "ref_data")
@@ -29,23 +29,6 @@ def _motif(W, seed=0):
     from grafimo_amd import synth
     rec = synth.synthetic_motif(W, np.random.default_rng(900 + 13 * W + seed), np.array([0.3, 0.2, 0.2, 0.3]))
     return synth.motif_object(rec, f"SYN{W}")
-
-
-def _check_bruteforce(hh, idx, regions, motif, args):
-    od = motif_as_oracle_dict(motif)
-    W = od["width"]
-    ptab = np.cumsum(od["pmf"][::-1])[::-1]
-    counts, best = haplotype_matrix(idx, regions, W, od["score_matrix"], od["min_val"], integer_cutoff(ptab, args.threshold),
-                                    forward_only=args.noreverse)
-    assert hh.counts.shape == counts.shape and hh.counts.dtype == np.int32
-    assert (hh.counts == counts).all(), np.argwhere(hh.counts != counts)[:5]
-    some = best >= 0
-    assert (hh.best == np.where(some, best, -1)).all()
-    exp_score = np.where(some, best / od["scale"] + W * od["offset"], np.nan)
-    assert np.array_equal(hh.best_score, exp_score, equal_nan=True)
-    exp_p = np.where(some, ptab[np.where(some, best, 0)], np.nan)
-    assert np.allclose(hh.best_pvalue, exp_p, rtol=1e-12, atol=0, equal_nan=True)
-    return counts
 
 
 @pytest.mark.parametrize("seed,W,kinds,no_reverse,threshold", [

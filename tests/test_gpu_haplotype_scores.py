@@ -15,8 +15,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-from extract_helpers import make_consistent_graph_files, motif_as_oracle_dict  # noqa: E402
-from haplotype_score_bruteforce import haplotype_score_keys  # noqa: E402
+from extract_helpers import make_consistent_graph_files  # noqa: E402
+from graph_table_checks import check_haplotype_scores as _check_bruteforce  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(ROOT, "tests", "golden", "ref_data")
@@ -37,35 +37,6 @@ def _motif(W, seed=0):
 def _ctcf():
     from grafimo_amd.motif_ops import build_motif_meme_host
     return build_motif_meme_host(os.path.join(GOLD, "MA0139.1.meme"), "unfrm_dst", 0.1, False)[0]
-
-
-def _check_bruteforce(hs, idx, regions, motif, forward_only):
-    """every cell against the brute force: the key bit for bit, and the fields made from it"""
-    from grafimo_amd.haplotype_scores import unpack_keys
-    od = motif_as_oracle_dict(motif)
-    W = od["width"]
-    exp = haplotype_score_keys(idx, regions, W, od["score_matrix"], od["min_val"], forward_only=forward_only)
-    assert hs.keys.shape == exp.shape
-    assert (hs.keys == exp).all(), np.argwhere(hs.keys != exp)[:5]
-    base = np.array([max(S, 0) for S, _ in regions], dtype=np.int64)[:, None]
-    best, left, right, plus = unpack_keys(exp, base)
-    ptab = np.cumsum(od["pmf"][::-1])[::-1]
-    some = best >= 0
-    full_best = np.concatenate([hs.best, hs.reference_best[:, None]], axis=1)
-    assert (full_best == best).all()
-    score = np.concatenate([hs.best_score, hs.reference_score[:, None]], axis=1)
-    assert np.array_equal(score, np.where(some, best / od["scale"] + W * od["offset"], np.nan), equal_nan=True)
-    pv = np.concatenate([hs.best_pvalue, hs.reference_pvalue[:, None]], axis=1)
-    assert np.allclose(pv, np.where(some, ptab[np.where(some, best, 0)], np.nan), rtol=1e-12, atol=0, equal_nan=True)
-    start = np.concatenate([hs.start, hs.reference_start[:, None]], axis=1)
-    stop = np.concatenate([hs.stop, hs.reference_stop[:, None]], axis=1)
-    strand = np.concatenate([hs.strand, hs.reference_strand[:, None]], axis=1)
-    assert (start == np.where(some, np.where(plus, left, right), -1)).all()
-    assert (stop == np.where(some, np.where(plus, right, left), -1)).all()
-    assert (strand == np.where(some, np.where(plus, "+", "-"), "")).all()
-    if forward_only:
-        assert not (strand == "-").any()
-    return best
 
 
 @pytest.mark.parametrize("seed,W,no_reverse", [(1, 5, False), (2, 8, True), (3, 12, False), (4, 19, True), (5, 30, False),

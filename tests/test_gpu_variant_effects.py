@@ -12,7 +12,8 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 from extract_helpers import make_consistent_graph_files, motif_as_oracle_dict  # noqa: E402
-from variant_bruteforce import best_hits, expected_rows  # noqa: E402
+from graph_table_checks import check_variant_effects as _check  # noqa: E402
+from variant_bruteforce import best_hits  # noqa: E402
 from variant_walks import best_hits_walks  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -29,33 +30,6 @@ def _motif(W, seed=0):
     from grafimo_amd import synth
     rec = synth.synthetic_motif(W, np.random.default_rng(500 + 11 * W + seed), np.array([0.3, 0.2, 0.2, 0.3]))
     return synth.motif_object(rec, f"SYN{W}")
-
-
-def _check(df, idx, regions, motif, args, all_sites, name=None, best=None):
-    from oracle import oracle as orc
-    od = motif_as_oracle_dict(motif)
-    W = od["width"]
-    if best is None:
-        best = best_hits(idx, regions, W, od["score_matrix"], od["min_val"], forward_only=args.noreverse)
-    ptab = np.cumsum(od["pmf"][::-1])[::-1]
-    exp = expected_rows(idx, best, ptab, args.threshold, all_sites)
-    assert len(df) == len(exp), (len(df), len(exp))
-    for row, ((i, a), (r, x, eff)) in zip(df.itertuples(index=False), sorted(exp.items())):
-        assert row.position == int(idx.pos[i]) + 1
-        assert row.effect == eff, (i, a, row.effect, eff)
-        for side, e in (("ref", r), ("alt", x)):
-            if e is None:
-                assert np.isnan(getattr(row, side + "_score")) and getattr(row, side + "_sequence") == ""
-                continue
-            sc, lo, pv = orc.score_kmers(np.frombuffer(e[4], dtype=np.uint8).reshape(1, W), od["score_matrix"], od["pmf"],
-                                         od["min_val"], od["scale"], od["offset"])
-            assert int(sc[0]) == e[0]
-            assert getattr(row, side + "_score") == e[0] / od["scale"] + W * od["offset"], (i, a, side)
-            assert (getattr(row, side + "_start"), getattr(row, side + "_stop"), getattr(row, side + "_strand"),
-                    getattr(row, side + "_sequence")) == (e[1], e[2], e[3], e[4].decode()), (i, a, side)
-            assert abs(getattr(row, side + "_pvalue") - pv[0]) <= 1e-12
-        if name is not None:
-            assert row.sequence_name == name
 
 
 @pytest.mark.parametrize("seed,W,no_reverse,all_sites", [

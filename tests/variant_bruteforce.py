@@ -91,6 +91,19 @@ def spell(idx, h: int):
     return out, coord, ins, single, junction
 
 
+def haplotype_classes(idx):
+    """-> (one haplotype of every class, the class of every haplotype): haplotypes with the same allele at every site spell
+    the same sequence, so a brute force may spell one per class (graphs of thousands of haplotypes over a few sites)"""
+    H = int(idx.n_haplotypes) if idx.alt_bits is not None else 0
+    if not H or not len(idx.pos):
+        return np.zeros(min(H, 1), dtype=np.int64), np.zeros(H, dtype=np.int64)
+    bits = np.unpackbits(np.ascontiguousarray(idx.alt_bits).view(np.uint8), axis=-1, bitorder="little")[..., :H]
+    used = np.arange(bits.shape[1])[None, :] < np.asarray(idx.n_alts, dtype=np.int64)[:, None]
+    alleles = (bits * used[..., None]).reshape(-1, H).T
+    _, first, inv = np.unique(alleles, axis=0, return_index=True, return_inverse=True)
+    return first.astype(np.int64), inv.reshape(-1).astype(np.int64)
+
+
 def revcomp(k: bytes) -> bytes:
     return k.translate(_COMP)[::-1]
 
@@ -102,13 +115,14 @@ def int_score(kmer: bytes, sm: np.ndarray, min_val: int) -> int:
     return int(sm[c, np.arange(len(kmer))].sum())
 
 
-def best_hits(idx, regions, W: int, sm: np.ndarray, min_val: int, forward_only: bool = False):
-    """-> {slot: (score, start, stop, strand, kmer bytes as printed)} over the haplotypes' windows in the regions."""
+def best_hits(idx, regions, W: int, sm: np.ndarray, min_val: int, forward_only: bool = False, memo: bool = False):
+    """-> {slot: (score, start, stop, strand, kmer bytes as printed)} over the haplotypes' windows in the regions.
+    `memo`: one haplotype per class of haplotype_classes (the same result)."""
     sm = np.asarray(sm, dtype=np.int64)
     H = int(idx.n_haplotypes) if idx.alt_bits is not None else 0
     L = len(idx.ref)
     cand: Dict[Tuple[bytes, int, int], set] = {}
-    for h in range(H):
+    for h in (haplotype_classes(idx)[0].tolist() if memo else range(H)):
         seq, coord, ins, single, junction = spell(idx, h)
         s_keys = [t[0] for t in single]
         j_keys = [t[0] for t in junction]
