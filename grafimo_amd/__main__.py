@@ -107,6 +107,12 @@ def get_parser():
     p.add_argument("--haplotype-scores", action="store_true", dest="haplotype_scores",
                    help="also write grafimo_haplotype_scores[_MOTIF].tsv (printed with -f): per region, each haplotype's best "
                         "motif score whatever the threshold, beside the reference's (graph routes only)")
+    p.add_argument("--hit-alleles", action="store_true", dest="hit_alleles",
+                   help="also write grafimo_hit_alleles[_MOTIF].tsv (printed with -f): the report's rows, each with the variant "
+                        "alleles that make its k-mer and, with --haplotype-groups, its carriers per group (graph routes only)")
+    p.add_argument("--haplotype-groups", dest="haplotype_groups", metavar="FILE",
+                   help="with --hit-alleles: SAMPLE GROUP lines (the 1000 Genomes panel file reads as is), one "
+                        "haplotypes_GROUP column per group")
     p.add_argument("-j", "--cores", type=int, default=0, help="host threads for TSV ingest (0 = all)")
     p.add_argument("-o", "--out", default=DEFAULT_OUTDIR)
     p.add_argument("--verbose", action="store_true")
@@ -194,6 +200,10 @@ def main(argv=None):
         sys.exit("ERROR: --haplotype-hits needs the graph (-g / -d with -b, or -l -v -b): the rows of -s carry no walks")
     if a.haplotype_scores and a.sequences:
         sys.exit("ERROR: --haplotype-scores needs the graph (-g / -d with -b, or -l -v -b): the rows of -s carry no walks")
+    if a.haplotype_groups and not a.hit_alleles:
+        sys.exit("ERROR: --haplotype-groups goes with --hit-alleles")
+    if a.hit_alleles and a.sequences:
+        sys.exit("ERROR: --hit-alleles needs the graph (-g / -d with -b, or -l -v -b): the rows of -s carry no walks")
     if not from_vg and (from_graph == bool(a.sequences) or (from_graph and not (a.linear_genome and a.vcf and a.bedfile))):
         sys.exit("ERROR: give -g XG / -d DIR with -b BED, or -s DIR, or all of -l FASTA -v VCF -b BED")
     if a.cores <= 0:
@@ -293,6 +303,29 @@ def main(argv=None):
                 continue
             path = write_haplotype_scores(hs, motif, len(motifs), wf)
             print(f"{hs.best.shape[0]} x {hs.best.shape[1]} haplotype best scores written to {path}")
+    if a.hit_alleles:
+        from .haplotype_hits import haplotype_column_names
+        from .hit_alleles import compute_hit_alleles_many, print_hit_alleles, read_haplotype_groups, write_hit_alleles
+        if from_vg:
+            from .extract_regions import _manifest_prep, read_manifest
+            manifest = read_manifest(sequences_loc)
+            if manifest is None:
+                sys.exit("ERROR: --hit-alleles needs the graph; scan_graph left TSV rows, which carry no walks")
+            source, source_regions = manifest, None
+            first_index = _manifest_prep(manifest).graphs[0].index
+        else:
+            source, source_regions = graphs, region_lists
+            first_index = graphs[0].index
+        groups = None
+        if a.haplotype_groups:
+            groups = read_haplotype_groups(a.haplotype_groups, haplotype_column_names(first_index))
+        tables = compute_hit_alleles_many(motifs, source, source_regions, a.debug, wf, haplotype_groups=groups)
+        for motif, ha in zip(motifs, tables):
+            if a.text_only:                            # -f: printed like the report, no file written
+                print_hit_alleles(ha)
+                continue
+            path = write_hit_alleles(ha, motif, len(motifs), wf)
+            print(f"{len(ha)} hit allele rows written to {path}")
     if sequences_loc:
         import shutil
         shutil.rmtree(sequences_loc, ignore_errors=True)

@@ -127,6 +127,10 @@ PROTOTYPES = {
     "gfm_graph_annotate": (c_int, [c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_void_p]),
     "gfm_graph_haplotype_hits": (c_int, [c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_i32, c_void_p, c_void_p, c_i64,
                                          c_void_p]),
+    "gfm_graph_hit_alleles": (c_int, [c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_i32, c_void_p, c_void_p, c_void_p, c_i64,
+                                      c_void_p, c_void_p, c_void_p, c_i64, c_void_p]),
+    "gfm_graph_hit_order": (c_int, [c_void_p, c_i32, c_i32, c_void_p, c_void_p, c_void_p, ctypes.c_uint32, P(c_i64), c_void_p,
+                                    c_void_p]),
     "gfm_graph_hit_columns": (c_int, [c_void_p, c_i32, c_i32, ctypes.c_double, c_i32, c_i32, c_void_p, c_void_p, c_void_p,
                                       c_void_p, ctypes.c_uint32, P(c_i64)] + [c_void_p] * 10),
     "gfm_graph_hit_columns_start": (c_int, [c_void_p, c_i32, P(c_void_p)]),

@@ -2508,3 +2508,4 @@ GFM_API int gfm_graph_annotate(gfm_graph_t g, const void *d_hits, const uint64_t
 #include "gfm_graph_variant.hpp"
 #include "gfm_graph_haplotypes.hpp"
 #include "gfm_graph_hapscores.hpp"
+#include "gfm_graph_hit_alleles.hpp"

@@ -52,6 +52,104 @@ inline bool key_less(const Key &a, const Key &b)      // inside one score: the o
     return a.part < b.part;
 }
 
+// scratch of report_order, kept per thread: a fresh 300 KB vector per call is an mmap and a page fault per 4 KB -- a third
+// of the call
+thread_local std::vector<Key> keys, sorted;
+thread_local std::vector<int32_t> canon;
+thread_local std::vector<int64_t> at, put;
+
+// ... but a call of millions of rows (GRAFIMO_MAX_HITS: 2^23) does not leave half a gigabyte behind: what is larger than
+// ~10 MB is given back when the call returns (the scratch is per THREAD: the jobs of a motif set run on several)
+struct Trim {
+    ~Trim()
+    {
+        constexpr size_t kKeepKeys = (size_t)1 << 18;
+        if (keys.capacity() > kKeepKeys) std::vector<Key>().swap(keys);
+        if (sorted.capacity() > kKeepKeys) std::vector<Key>().swap(sorted);
+        if (canon.capacity() > 8 * kKeepKeys) std::vector<int32_t>().swap(canon);
+        if (at.capacity() > 4 * kKeepKeys) std::vector<int64_t>().swap(at);
+        if (put.capacity() > 4 * kKeepKeys) std::vector<int64_t>().swap(put);
+    }
+};
+
+// The report's selection and order, for gfm_graph_hit_columns and gfm_graph_hit_order alike: the records that are kept
+// (keep flag, --recomb filter) into this thread's `keys` in report order.  `who`: the entry point's name for the messages.
+int report_order(const char *who, const double *h_ptable, int32_t table_len, int32_t n_parts,
+                 const gfm_graph_hit_t *const *h_recs, const int64_t *n_recs, const int64_t *const *h_entry_of,
+                 uint32_t flags, int threads)
+{
+    const std::string name(who);
+    int64_t total = 0;
+    for (int p = 0; p < n_parts; ++p) {
+        if (n_recs[p] < 0 || (n_recs[p] && !h_recs[p])) return hfail(GFM_ERR_INVALID, name + ": bad part");
+        total += n_recs[p];
+    }
+    const bool drop_zero = (flags & GFM_HITS_DROP_ZERO_FREQ) != 0;
+    // Report order = p-value ascending, rows of one p-value in the order of the TSV rows.  The p-value is a table lookup
+    // on the integer score and never rises with it, so: rows into buckets by score (a counting sort; scores that share a
+    // p-value -- a stretch of the tail table where the pmf is 0 -- share the bucket of the stretch's lowest score), buckets
+    // from the highest score down, and inside a bucket a sort by (entry, window, walk * 2 + strand).  A comparison sort of
+    // all rows by (p, entry, window, walk) took 0.65 ms for 6 000 rows -- a mispredicted branch per comparison.
+    keys.clear();
+    keys.reserve((size_t)total);
+    int32_t lo_s = INT32_MAX, hi_s = -1;
+    for (int p = 0; p < n_parts; ++p) {
+        const gfm_graph_hit_t *r = h_recs[p];
+        const int64_t *eo = h_entry_of ? h_entry_of[p] : nullptr;
+        for (int64_t i = 0; i < n_recs[p]; ++i) {
+            if (!r[i].keep) continue;                                   // a p < t candidate the q-value cutoff dropped
+            if (drop_zero && r[i].freq <= 0) continue;                  // resultsTmp.py:309-310
+            const int32_t sc = r[i].score;
+            if (sc < 0 || sc >= table_len) return hfail(GFM_ERR_INVALID, name + ": a score outside the table");
+            const int64_t e = eo ? eo[r[i].region] : 0;
+            if (e < 0 || e > INT32_MAX || r[i].w < 0) return hfail(GFM_ERR_INVALID, name + ": entry rank / window out of range");
+            keys.push_back(Key{(uint64_t)e << 32 | (uint32_t)r[i].w, r[i].q2, sc, p, &r[i]});
+            lo_s = std::min(lo_s, sc);
+            hi_s = std::max(hi_s, sc);
+        }
+    }
+    const int64_t n = (int64_t)keys.size();
+    if (!n) return GFM_OK;
+    const int32_t span = hi_s - lo_s + 1;
+    canon.resize((size_t)span);                                     // score -> the lowest score >= lo_s with its p-value
+    for (int32_t sc = lo_s; sc <= hi_s; ++sc)
+        canon[(size_t)(sc - lo_s)] = (sc > lo_s && h_ptable[sc] == h_ptable[sc - 1]) ? canon[(size_t)(sc - 1 - lo_s)] : sc;
+    at.assign((size_t)span + 1, 0);                                 // bucket b = hi_s - canon: highest score first
+    for (Key &k : keys) {
+        k.cs = canon[(size_t)(k.cs - lo_s)];
+        ++at[(size_t)(hi_s - k.cs) + 1];
+    }
+    for (int32_t b = 0; b < span; ++b) at[(size_t)b + 1] += at[(size_t)b];
+    sorted.resize((size_t)n);
+    put.assign(at.begin(), at.end() - 1);
+    for (const Key &k : keys) sorted[(size_t)put[(size_t)(hi_s - k.cs)]++] = k;
+    Key *const sp = sorted.data();
+    const int64_t *const atp = at.data();
+    auto sort_buckets = [sp, atp](int32_t b0, int32_t b1) {
+        for (int32_t b = b0; b < b1; ++b)
+            if (atp[b + 1] - atp[b] > 1) std::sort(sp + atp[b], sp + atp[b + 1], key_less);
+    };
+    if (threads > 1 && n >= kThreadedRows) {
+        // (one table for ONE motif -- GRAFIMO's loop makes a call per motif, grafimo.py:177-183 --: the buckets and, in
+        //  the callers, the rows of the output dealt to a few of the library's host threads; the caller's thread local
+        //  vectors are read through plain pointers there)
+        std::atomic<int32_t> next{0};
+        const int32_t step = std::max<int32_t>(16, span / (8 * threads));
+        const bool helped = gfm_workers::run_if_idle(threads, [&] {
+            for (;;) {
+                const int32_t b0 = next.fetch_add(step, std::memory_order_relaxed);
+                if (b0 >= span) break;
+                sort_buckets(b0, std::min(span, b0 + step));
+            }
+        });
+        if (!helped) sort_buckets(0, span);        // (the threads are busy with somebody else's work: alone, then)
+    } else {
+        sort_buckets(0, span);
+    }
+    keys.swap(sorted);
+    return GFM_OK;
+}
+
 int hit_columns(const double *h_ptable, int32_t table_len, int32_t scale, double offset, int32_t width,
                 int32_t n_parts, const gfm_graph_hit_t *const *h_recs,
                 const int64_t *n_recs, const int64_t *const *h_entry_of, const int64_t *region_base,
@@ -62,92 +160,11 @@ int hit_columns(const double *h_ptable, int32_t table_len, int32_t scale, double
     if (!h_ptable || table_len < 1 || scale == 0 || !n_out || n_parts < 0 || (n_parts && (!h_recs || !n_recs)) || width < 1 || width > GFM_MAX_WIDTH)
         return hfail(GFM_ERR_INVALID, "gfm_graph_hit_columns: bad argument");
     try {
-        int64_t total = 0;
-        for (int p = 0; p < n_parts; ++p) {
-            if (n_recs[p] < 0 || (n_recs[p] && !h_recs[p])) return hfail(GFM_ERR_INVALID, "gfm_graph_hit_columns: bad part");
-            total += n_recs[p];
-        }
-        const bool drop_zero = (flags & GFM_HITS_DROP_ZERO_FREQ) != 0;
-        // Report order = p-value ascending, rows of one p-value in the order of the TSV rows.  The p-value is a table lookup
-        // on the integer score and never rises with it, so: rows into buckets by score (a counting sort; scores that share a
-        // p-value -- a stretch of the tail table where the pmf is 0 -- share the bucket of the stretch's lowest score), buckets
-        // from the highest score down, and inside a bucket a sort by (entry, window, walk * 2 + strand).  A comparison sort of
-        // all rows by (p, entry, window, walk) took 0.65 ms for 6 000 rows -- a mispredicted branch per comparison.
-        // (scratch kept per thread: a fresh 300 KB vector per call is an mmap and a page fault per 4 KB -- a third of the call)
-        static thread_local std::vector<Key> keys, sorted;
-        static thread_local std::vector<int32_t> canon;
-        static thread_local std::vector<int64_t> at, put;
-        // ... but a call of millions of rows (GRAFIMO_MAX_HITS: 2^23) does not leave half a gigabyte behind: what is larger than
-        // ~10 MB is given back when the call returns (the scratch is per THREAD: the jobs of a motif set run on several)
-        struct Trim {
-            ~Trim()
-            {
-                constexpr size_t kKeepKeys = (size_t)1 << 18;
-                if (keys.capacity() > kKeepKeys) std::vector<Key>().swap(keys);
-                if (sorted.capacity() > kKeepKeys) std::vector<Key>().swap(sorted);
-                if (canon.capacity() > 8 * kKeepKeys) std::vector<int32_t>().swap(canon);
-                if (at.capacity() > 4 * kKeepKeys) std::vector<int64_t>().swap(at);
-                if (put.capacity() > 4 * kKeepKeys) std::vector<int64_t>().swap(put);
-            }
-        } trim;
-        keys.clear();
-        keys.reserve((size_t)total);
-        int32_t lo_s = INT32_MAX, hi_s = -1;
-        for (int p = 0; p < n_parts; ++p) {
-            const gfm_graph_hit_t *r = h_recs[p];
-            const int64_t *eo = h_entry_of ? h_entry_of[p] : nullptr;
-            for (int64_t i = 0; i < n_recs[p]; ++i) {
-                if (!r[i].keep) continue;                                   // a p < t candidate the q-value cutoff dropped
-                if (drop_zero && r[i].freq <= 0) continue;                  // resultsTmp.py:309-310
-                const int32_t sc = r[i].score;
-                if (sc < 0 || sc >= table_len) return hfail(GFM_ERR_INVALID, "gfm_graph_hit_columns: a score outside the table");
-                const int64_t e = eo ? eo[r[i].region] : 0;
-                if (e < 0 || e > INT32_MAX || r[i].w < 0) return hfail(GFM_ERR_INVALID, "gfm_graph_hit_columns: entry rank / window out of range");
-                keys.push_back(Key{(uint64_t)e << 32 | (uint32_t)r[i].w, r[i].q2, sc, p, &r[i]});
-                lo_s = std::min(lo_s, sc);
-                hi_s = std::max(hi_s, sc);
-            }
-        }
+        Trim trim;
+        if (const int rc = report_order("gfm_graph_hit_columns", h_ptable, table_len, n_parts, h_recs, n_recs, h_entry_of, flags,
+                                        threads))
+            return rc;
         const int64_t n = (int64_t)keys.size();
-        if (n) {
-            const int32_t span = hi_s - lo_s + 1;
-            canon.resize((size_t)span);                                     // score -> the lowest score >= lo_s with its p-value
-            for (int32_t sc = lo_s; sc <= hi_s; ++sc)
-                canon[(size_t)(sc - lo_s)] = (sc > lo_s && h_ptable[sc] == h_ptable[sc - 1]) ? canon[(size_t)(sc - 1 - lo_s)] : sc;
-            at.assign((size_t)span + 1, 0);                                 // bucket b = hi_s - canon: highest score first
-            for (Key &k : keys) {
-                k.cs = canon[(size_t)(k.cs - lo_s)];
-                ++at[(size_t)(hi_s - k.cs) + 1];
-            }
-            for (int32_t b = 0; b < span; ++b) at[(size_t)b + 1] += at[(size_t)b];
-            sorted.resize((size_t)n);
-            put.assign(at.begin(), at.end() - 1);
-            for (const Key &k : keys) sorted[(size_t)put[(size_t)(hi_s - k.cs)]++] = k;
-            Key *const sp = sorted.data();
-            const int64_t *const atp = at.data();
-            auto sort_buckets = [sp, atp](int32_t b0, int32_t b1) {
-                for (int32_t b = b0; b < b1; ++b)
-                    if (atp[b + 1] - atp[b] > 1) std::sort(sp + atp[b], sp + atp[b + 1], key_less);
-            };
-            if (threads > 1 && n >= kThreadedRows) {
-                // (one table for ONE motif -- GRAFIMO's loop makes a call per motif, grafimo.py:177-183 --: the buckets and, below,
-                //  the rows of the output dealt to a few of the library's host threads; the caller's thread local vectors are
-                //  read through plain pointers there)
-                std::atomic<int32_t> next{0};
-                const int32_t step = std::max<int32_t>(16, span / (8 * threads));
-                const bool helped = gfm_workers::run_if_idle(threads, [&] {
-                    for (;;) {
-                        const int32_t b0 = next.fetch_add(step, std::memory_order_relaxed);
-                        if (b0 >= span) break;
-                        sort_buckets(b0, std::min(span, b0 + step));
-                    }
-                });
-                if (!helped) sort_buckets(0, span);        // (the threads are busy with somebody else's work: alone, then)
-            } else {
-                sort_buckets(0, span);
-            }
-            keys.swap(sorted);
-        }
         int64_t out = 0;
         std::vector<uint8_t> seen;                   // GFM_HITS_FIRST_PER_REGION: one row per region, its first in report order
         const bool first_only = (flags & GFM_HITS_FIRST_PER_REGION) != 0;
@@ -212,6 +229,32 @@ int hit_columns(const double *h_ptable, int32_t table_len, int32_t scale, double
     }
 }
 
+// which record became which row: the (part, record index) of every row of the report order
+int hit_order(const double *h_ptable, int32_t table_len, int32_t n_parts, const gfm_graph_hit_t *const *h_recs,
+              const int64_t *n_recs, const int64_t *const *h_entry_of, uint32_t flags, int64_t *n_out, int32_t *o_part,
+              int64_t *o_index, int threads)
+{
+    if (!h_ptable || table_len < 1 || !n_out || n_parts < 0 || (n_parts && (!h_recs || !n_recs)))
+        return hfail(GFM_ERR_INVALID, "gfm_graph_hit_order: bad argument");
+    if (flags & GFM_HITS_FIRST_PER_REGION)
+        return hfail(GFM_ERR_INVALID, "gfm_graph_hit_order: GFM_HITS_FIRST_PER_REGION is not supported (the rows of the whole report only)");
+    try {
+        Trim trim;
+        if (const int rc = report_order("gfm_graph_hit_order", h_ptable, table_len, n_parts, h_recs, n_recs, h_entry_of, flags, threads))
+            return rc;
+        const int64_t n = (int64_t)keys.size();
+        for (int64_t j = 0; j < n; ++j) {
+            const Key &k = keys[(size_t)j];
+            if (o_part) o_part[j] = k.part;
+            if (o_index) o_index[j] = (int64_t)(k.rec - h_recs[k.part]);
+        }
+        *n_out = n;
+        return GFM_OK;
+    } catch (const std::bad_alloc &) {
+        return hfail(GFM_ERR_NOMEM, "gfm_graph_hit_order: out of host memory");
+    }
+}
+
 }   // namespace
 
 GFM_API int gfm_graph_hit_columns(const double *h_ptable, int32_t table_len, int32_t scale, double offset, int32_t width,
@@ -226,6 +269,14 @@ GFM_API int gfm_graph_hit_columns(const double *h_ptable, int32_t table_len, int
     const int threads = (int)std::min(4u, std::max(2u, std::thread::hardware_concurrency()) / 2);
     return hit_columns(h_ptable, table_len, scale, offset, width, n_parts, h_recs, n_recs, h_entry_of, region_base, flags, n_out,
                        o_start, o_stop, o_freq, o_region, o_score, o_pvalue, o_qvalue, o_strand, o_ref, o_kmers, threads);
+}
+
+GFM_API int gfm_graph_hit_order(const double *h_ptable, int32_t table_len, int32_t n_parts, const gfm_graph_hit_t *const *h_recs,
+                                const int64_t *n_recs, const int64_t *const *h_entry_of, uint32_t flags, int64_t *n_out,
+                                int32_t *o_part, int64_t *o_index)
+{
+    const int threads = (int)std::min(4u, std::max(2u, std::thread::hardware_concurrency()) / 2);
+    return hit_order(h_ptable, table_len, n_parts, h_recs, n_recs, h_entry_of, flags, n_out, o_part, o_index, threads);
 }
 
 // The tables of a motif SET: one job per motif, taken by the library's kept host threads while the caller goes on -- in

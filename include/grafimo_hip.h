@@ -518,6 +518,29 @@ int gfm_graph_annotate(gfm_graph_t g, const void *d_hits, const uint64_t *d_hit_
 int gfm_graph_haplotype_hits(gfm_graph_t g, const void *d_hits, const uint64_t *d_hit_count, int64_t hit_capacity,
                              const int32_t *d_cutoff, int32_t n_regions, int32_t *d_counts, int32_t *d_best,
                              int64_t scratch_bytes, void *stream);
+/* The per-hit allele table of the entries of the LAST gfm_graph_score[_multi] call, the same list gfm_graph_annotate serves,
+ * indexed by the ENTRY index i (record i of gfm_graph_annotate).  For every entry with score >= *d_cutoff (d_cutoff NULL:
+ * all; --qvalueT as in annotate):
+ *   its alleles: the SET of (site, allele) constraints of its walk -- the constraints the haplotype counting ANDs: allele 0 =
+ *     REF, 1..3 = ALT of a substitution site; 1 = an insertion read / a deletion jumped, 0 = passed by / its bases used / a
+ *     deletion that would cover the window's first base -- packed site * 4 + allele, ascending, no pair twice, as CSR:
+ *     d_allele_off int64 [hit_capacity + 1] (always written in full), d_alleles int32 [allele_capacity].  Constraints beyond
+ *     allele_capacity are dropped: d_allele_off[hit_capacity] says how much room to come back with (allele_capacity 0 and
+ *     d_alleles NULL: only ask);
+ *   d_group_counts int32 [hit_capacity][n_groups]: the carriers of the entry -- the AND of the constraints' bitsets, the set
+ *     whose size is the record's freq -- in each group, popcount(carriers & group).  d_group_bits uint64 [n_groups][hw]
+ *     (hw = ceil(n_hap / 64), haplotype h = bit h & 63 of word h >> 6); groups may overlap and need not cover the haplotypes;
+ *     n_groups 0 .. 64 (more: GFM_ERR_INVALID, nothing is truncated);
+ *   d_total int32 [hit_capacity] (optional): the size of the carrier set, the kernel's own count of the record's freq;
+ *   d_masks uint64 [hit_capacity][hw] (optional): the carrier set itself, the bits beyond n_hap clear.
+ * Entries under the cutoff and slots behind *d_hit_count have no alleles and zeros everywhere.  A graph without haplotype
+ * bitsets still gives the alleles; n_groups > 0, d_total or d_masks on it is GFM_ERR_INVALID.  scratch_bytes bounds the
+ * device scratch (<= 0: 256 MB): the entries are taken in batches whose staging fits it; the result does not depend on it.
+ * Enqueue only (stream-ordered device scratch); calls of one handle are serialised as gfm_graph_score's are. */
+int gfm_graph_hit_alleles(gfm_graph_t g, const void *d_hits, const uint64_t *d_hit_count, int64_t hit_capacity,
+                          const int32_t *d_cutoff, int32_t n_groups, const uint64_t *d_group_bits, int64_t *d_allele_off,
+                          int32_t *d_alleles, int64_t allele_capacity, int32_t *d_group_counts, int32_t *d_total,
+                          uint64_t *d_masks, int64_t scratch_bytes, void *stream);
 
 /* ------------------------------------------------------------------ the report's rows from the hit records (host)
  * replaces what ResultTmp.to_df does with the rows that passed the threshold (resultsTmp.py:303-314): the --recomb filter
@@ -544,6 +567,14 @@ int gfm_graph_hit_columns(const double *h_ptable, int32_t table_len, int32_t sca
                           uint32_t flags, int64_t *n_out, int64_t *o_start, int64_t *o_stop, int64_t *o_freq,
                           int64_t *o_region, double *o_score, double *o_pvalue, double *o_qvalue, uint8_t *o_strand,
                           uint8_t *o_ref, uint8_t *o_kmers);
+/* Which record became which row: the selection and order of gfm_graph_hit_columns (the same code runs) for the same h_ptable,
+ * parts, h_entry_of and flags -> for output row j of that table, o_part[j] = the part and o_index[j] = the index in
+ * h_recs[o_part[j]] of the record it was made from (caller-allocated for sum(n_recs) rows, either may be NULL); *n_out =
+ * rows.  What is kept per hit ENTRY beside the records (gfm_graph_hit_alleles) is gathered into report order with it.
+ * GFM_HITS_FIRST_PER_REGION is refused (GFM_ERR_INVALID). */
+int gfm_graph_hit_order(const double *h_ptable, int32_t table_len, int32_t n_parts, const gfm_graph_hit_t *const *h_recs,
+                        const int64_t *n_recs, const int64_t *const *h_entry_of, uint32_t flags, int64_t *n_out,
+                        int32_t *o_part, int64_t *o_index);
 /* gfm_graph_hit_columns for the motifs of a SET without holding the caller -- grafimo.findmotif builds one table per motif
  * of the set (grafimo.py:177-183), and what a Python caller does with a table's columns next (strings, a DataFrame) holds
  * the interpreter: the jobs -- one per motif, the arguments of gfm_graph_hit_columns as a struct; `status` and `n_out`
