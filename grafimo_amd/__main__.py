@@ -111,8 +111,15 @@ def get_parser():
                    help="also write grafimo_hit_alleles[_MOTIF].tsv (printed with -f): the report's rows, each with the variant "
                         "alleles that make its k-mer and, with --haplotype-groups, its carriers per group (graph routes only)")
     p.add_argument("--haplotype-groups", dest="haplotype_groups", metavar="FILE",
-                   help="with --hit-alleles: SAMPLE GROUP lines (the 1000 Genomes panel file reads as is), one "
+                   help="with --hit-alleles or --hit-pairs: SAMPLE GROUP lines (the 1000 Genomes panel file reads as is), one "
                         "haplotypes_GROUP column per group")
+    p.add_argument("--hit-pairs", action="store_true", dest="hit_pairs",
+                   help="also write grafimo_hit_pairs.tsv (printed with -f): the pairs of report rows -- of one motif or of "
+                        "two -- of a region that lie within --pair-gap of each other and share carrier haplotypes, with how "
+                        "many haplotypes carry both (graph routes only)")
+    p.add_argument("--pair-gap", dest="pair_gap", nargs=2, type=int, default=None, metavar=("MIN", "MAX"),
+                   help="with --hit-pairs: the reference bases between the two rows of a pair, MIN <= gap <= MAX (negative: "
+                        "overlapping by that many); default 0 50")
     p.add_argument("-j", "--cores", type=int, default=0, help="host threads for TSV ingest (0 = all)")
     p.add_argument("-o", "--out", default=DEFAULT_OUTDIR)
     p.add_argument("--verbose", action="store_true")
@@ -200,8 +207,14 @@ def main(argv=None):
         sys.exit("ERROR: --haplotype-hits needs the graph (-g / -d with -b, or -l -v -b): the rows of -s carry no walks")
     if a.haplotype_scores and a.sequences:
         sys.exit("ERROR: --haplotype-scores needs the graph (-g / -d with -b, or -l -v -b): the rows of -s carry no walks")
-    if a.haplotype_groups and not a.hit_alleles:
-        sys.exit("ERROR: --haplotype-groups goes with --hit-alleles")
+    if a.haplotype_groups and not (a.hit_alleles or a.hit_pairs):
+        sys.exit("ERROR: --haplotype-groups goes with --hit-alleles or --hit-pairs")
+    if a.pair_gap is not None and not a.hit_pairs:
+        sys.exit("ERROR: --pair-gap goes with --hit-pairs")
+    if a.pair_gap is not None and a.pair_gap[0] > a.pair_gap[1]:
+        sys.exit(f"ERROR: --pair-gap MIN MAX: {a.pair_gap[0]} > {a.pair_gap[1]}")
+    if a.hit_pairs and a.sequences:
+        sys.exit("ERROR: --hit-pairs needs the graph (-g / -d with -b, or -l -v -b): the rows of -s carry no walks")
     if a.hit_alleles and a.sequences:
         sys.exit("ERROR: --hit-alleles needs the graph (-g / -d with -b, or -l -v -b): the rows of -s carry no walks")
     if not from_vg and (from_graph == bool(a.sequences) or (from_graph and not (a.linear_genome and a.vcf and a.bedfile))):
@@ -326,6 +339,31 @@ def main(argv=None):
                 continue
             path = write_hit_alleles(ha, motif, len(motifs), wf)
             print(f"{len(ha)} hit allele rows written to {path}")
+    if a.hit_pairs:
+        from .haplotype_hits import haplotype_column_names
+        from .hit_alleles import read_haplotype_groups
+        from .hit_pairs import compute_hit_pairs, print_hit_pairs, write_hit_pairs
+        if from_vg:
+            from .extract_regions import _manifest_prep, read_manifest
+            manifest = read_manifest(sequences_loc)
+            if manifest is None:
+                sys.exit("ERROR: --hit-pairs needs the graph; scan_graph left TSV rows, which carry no walks")
+            source, source_regions = manifest, None
+            first_index = _manifest_prep(manifest).graphs[0].index
+        else:
+            source, source_regions = graphs, region_lists
+            first_index = graphs[0].index
+        groups = None
+        if a.haplotype_groups:
+            groups = read_haplotype_groups(a.haplotype_groups, haplotype_column_names(first_index))
+        min_gap, max_gap = a.pair_gap if a.pair_gap is not None else (0, 50)
+        hp = compute_hit_pairs(motifs, source, source_regions, a.debug, wf, haplotype_groups=groups, min_gap=min_gap,
+                               max_gap=max_gap)
+        if a.text_only:                                # -f: printed like the report, no file written
+            print_hit_pairs(hp)
+        else:
+            path = write_hit_pairs(hp, wf)
+            print(f"{len(hp)} hit pair rows written to {path}")
     if sequences_loc:
         import shutil
         shutil.rmtree(sequences_loc, ignore_errors=True)

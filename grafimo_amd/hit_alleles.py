@@ -26,7 +26,7 @@ import pandas as pd
 
 from . import _native as nv
 from .extract_regions import _FusedPass, _manifest_prep, _prepare_entries, _stream_ptr, _torch
-from .haplotype_hits import _haplotype_set
+from .haplotype_hits import _haplotype_set, _matrix_rows
 
 MAX_GROUPS = 64
 # room for the constraints of a call's first try, per hit entry (a walk has a handful); tests set it to 0 to take the path
@@ -42,10 +42,12 @@ class HitAlleles:
     allele_site     int32: the graph site;  allele uint8: 0 = REF, 1..3 = ALT;
     group_names     [G];  group_counts int32 [n, G];
     carrier_bits    uint64 [n, hw] or None;  haplotype_names [H] (empty for a graph without haplotypes);
-    indexes         per chromosome entry its GraphIndex (None for an entry without regions)."""
+    indexes         per chromosome entry its GraphIndex (None for an entry without regions);
+    row_region      int64 [n] or None: the region listing of every row -- the index into the caller's flattened region list
+                    (entries in order, regions in order; a region listed twice is two listings)."""
 
     def __init__(self, report: pd.DataFrame, allele_offsets, allele_entry, allele_site, allele, group_names, group_counts,
-                 carrier_bits, haplotype_names, indexes):
+                 carrier_bits, haplotype_names, indexes, *, row_region=None):
         self.report = report
         self.allele_offsets = np.asarray(allele_offsets, dtype=np.int64)
         self.allele_entry = np.asarray(allele_entry, dtype=np.int32)
@@ -56,6 +58,7 @@ class HitAlleles:
         self.carrier_bits = carrier_bits
         self.haplotype_names = list(haplotype_names)
         self.indexes = list(indexes)
+        self.row_region = None if row_region is None else np.asarray(row_region, dtype=np.int64)
 
     def __len__(self) -> int:
         return len(self.report)
@@ -301,6 +304,7 @@ def compute_hit_alleles_many(motifs: Sequence, graph, regions, debug: bool, args
     for g, eo in zip(prep.graphs, prep.entry_of):
         for e in np.unique(eo).tolist():
             indexes[int(e)] = g.index
+    listing_of = _matrix_rows(prep)[0]                  # per graph handle: the caller's region listing of its regions
     out: List[Optional[HitAlleles]] = [None] * len(motifs)
     by_width = {}
     for i, m in enumerate(motifs):
@@ -336,7 +340,14 @@ def compute_hit_alleles_many(motifs: Sequence, graph, regions, debug: bool, args
                 offsets, a_entry, a_site, a_allele, gc, masks = gathered[m]
                 if len(frames[m]) != len(offsets) - 1:
                     raise RuntimeError("the report and its order disagree on the number of rows")
-                out[i] = HitAlleles(frames[m], offsets, a_entry, a_site, a_allele, group_names, gc, masks, names, indexes)
+                part, index = orders[m]
+                row_region = np.zeros(len(part), dtype=np.int64)
+                for gi in range(len(prep.graphs)):
+                    rows = np.flatnonzero(part == gi)
+                    if len(rows):
+                        row_region[rows] = listing_of[gi][p.got[m][gi][3]["region"][index[rows]]]
+                out[i] = HitAlleles(frames[m], offsets, a_entry, a_site, a_allele, group_names, gc, masks, names, indexes,
+                                    row_region=row_region)
         finally:
             p.close()
     return out

@@ -667,6 +667,27 @@ int gfm_graph_haplotype_scores(gfm_graph_t g, const gfm_motif_t *motifs, int32_t
                                const int64_t *h_starts, const int64_t *h_stops, uint32_t flags, uint64_t *const *d_keys,
                                int32_t *d_overflow, int32_t windows_per_run, int32_t haplotypes_per_block, void *stream);
 
+/* ------------------------------------------------------------------ hit pairs: rows close to each other that share carriers
+ * Graph-independent (csrc/hit_pairs.hip).  n rows (n < 2^31 - 1) in device memory, in ascending (d_group, d_lo) order:
+ * d_group int32, d_lo <= d_hi int64 (|x| < 2^61), d_masks uint64 [n][hw] (hw >= 1 words of a bitset whose unused tail
+ * bits are CLEAR: the library does not mask them), optionally d_group_bits uint64 [n_groups][hw], n_groups 0 .. 64.
+ * A pair is two rows a < b of one group with min_gap <= gap <= max_gap, gap = max(lo_a, lo_b) - min(hi_a, hi_b) (negative:
+ * they overlap by that much), and joint = popcount(mask_a & mask_b) > 0.  The result is a CSR over the first row of a pair:
+ *   d_pair_off int64 [n + 1]: the pairs of row a are d_pair_off[a] .. d_pair_off[a + 1] - 1; *h_total = d_pair_off[n];
+ *   d_pair_b int32 [pair_capacity]: the partner b > a, ascending within a row;  d_joint int32: joint;
+ *   d_group_counts int32 [pair_capacity][n_groups]: popcount(mask_a & mask_b & group_g).
+ * Count first, then allocate: the pair arrays are written only when pair_capacity >= *h_total (else they are untouched and
+ * may be NULL with pair_capacity 0); the caller reads *h_total and comes back with room.  GFM_PAIRS_HAVE_OFFSETS: d_pair_off
+ * already holds the offsets an earlier call made for the same rows and gap, the counting pass is not run again.
+ * The order is CHECKED on the device: rows not ascending in (group, lo), lo > hi or a coordinate beyond the limit give
+ * GFM_ERR_INVALID and no pair.  Rows of equal (group, lo) may come in any order; that order decides which of two rows is
+ * `a`.  The call WAITS for the stream (it reads the verdict of the check and the total). */
+#define GFM_PAIRS_HAVE_OFFSETS 1u
+int gfm_hit_pairs(const int32_t *d_group, const int64_t *d_lo, const int64_t *d_hi, const uint64_t *d_masks, int64_t n,
+                  int32_t hw, int64_t min_gap, int64_t max_gap, int32_t n_groups, const uint64_t *d_group_bits,
+                  int64_t *d_pair_off, int64_t pair_capacity, int32_t *d_pair_b, int32_t *d_joint, int32_t *d_group_counts,
+                  uint32_t flags, int64_t *h_total, void *stream);
+
 /* Phased VCF (plain or gzip/bgzip) -> the site arrays of gfm_graph_create for one chromosome; host
  * threads parse the lines.  The reference hands the VCF to `vg construct` / `vg index -G`
  * (constructVG.py:332,394); here every ALT allele is taken apart: single-base substitutions (one site per
