@@ -120,6 +120,14 @@ def get_parser():
     p.add_argument("--pair-gap", dest="pair_gap", nargs=2, type=int, default=None, metavar=("MIN", "MAX"),
                    help="with --hit-pairs: the reference bases between the two rows of a pair, MIN <= gap <= MAX (negative: "
                         "overlapping by that many); default 0 50")
+    p.add_argument("--hit-linkage", action="store_true", dest="hit_linkage",
+                   help="also write grafimo_hit_linkage[_MOTIF].tsv (printed with -f): per report row the variant alleles "
+                        "within --linkage-flank of it whose carriers are in linkage disequilibrium with the row's, "
+                        "r2 >= --linkage-r2, with r2, r and D' (graph routes only)")
+    p.add_argument("--linkage-flank", dest="linkage_flank", type=int, default=None, metavar="N",
+                   help="with --hit-linkage: the reference bases around a row in which variants are tested; default 10000")
+    p.add_argument("--linkage-r2", dest="linkage_r2", type=float, default=None, metavar="X",
+                   help="with --hit-linkage: the smallest r2 listed, 0 .. 1; default 0.8")
     p.add_argument("-j", "--cores", type=int, default=0, help="host threads for TSV ingest (0 = all)")
     p.add_argument("-o", "--out", default=DEFAULT_OUTDIR)
     p.add_argument("--verbose", action="store_true")
@@ -215,6 +223,14 @@ def main(argv=None):
         sys.exit(f"ERROR: --pair-gap MIN MAX: {a.pair_gap[0]} > {a.pair_gap[1]}")
     if a.hit_pairs and a.sequences:
         sys.exit("ERROR: --hit-pairs needs the graph (-g / -d with -b, or -l -v -b): the rows of -s carry no walks")
+    if (a.linkage_flank is not None or a.linkage_r2 is not None) and not a.hit_linkage:
+        sys.exit("ERROR: --linkage-flank and --linkage-r2 go with --hit-linkage")
+    if a.linkage_flank is not None and a.linkage_flank < 0:
+        sys.exit(f"ERROR: --linkage-flank {a.linkage_flank} < 0")
+    if a.linkage_r2 is not None and not 0.0 <= a.linkage_r2 <= 1.0:
+        sys.exit(f"ERROR: --linkage-r2 {a.linkage_r2} outside [0, 1]")
+    if a.hit_linkage and a.sequences:
+        sys.exit("ERROR: --hit-linkage needs the graph (-g / -d with -b, or -l -v -b): the rows of -s carry no walks")
     if a.hit_alleles and a.sequences:
         sys.exit("ERROR: --hit-alleles needs the graph (-g / -d with -b, or -l -v -b): the rows of -s carry no walks")
     if not from_vg and (from_graph == bool(a.sequences) or (from_graph and not (a.linear_genome and a.vcf and a.bedfile))):
@@ -364,6 +380,25 @@ def main(argv=None):
         else:
             path = write_hit_pairs(hp, wf)
             print(f"{len(hp)} hit pair rows written to {path}")
+    if a.hit_linkage:
+        from .hit_linkage import compute_hit_linkage_many, print_hit_linkage, write_hit_linkage
+        if from_vg:
+            from .extract_regions import read_manifest
+            manifest = read_manifest(sequences_loc)
+            if manifest is None:
+                sys.exit("ERROR: --hit-linkage needs the graph; scan_graph left TSV rows, which carry no walks")
+            source, source_regions = manifest, None
+        else:
+            source, source_regions = graphs, region_lists
+        linkage = compute_hit_linkage_many(motifs, source, source_regions, a.debug, wf,
+                                           flank=10000 if a.linkage_flank is None else a.linkage_flank,
+                                           min_r2=0.8 if a.linkage_r2 is None else a.linkage_r2)
+        for motif, hl in zip(motifs, linkage):
+            if a.text_only:                            # -f: printed like the report, no file written
+                print_hit_linkage(hl)
+                continue
+            path = write_hit_linkage(hl, motif, len(motifs), wf)
+            print(f"{len(hl)} hit linkage rows written to {path}")
     if sequences_loc:
         import shutil
         shutil.rmtree(sequences_loc, ignore_errors=True)

@@ -35,6 +35,7 @@ GFM_HITS_FIRST_PER_REGION = 2
 GFM_VARIANT_ALL_SITES = 1
 GFM_VARIANT_KEEP_ZERO_FREQ = 2
 GFM_PAIRS_HAVE_OFFSETS = 1
+GFM_LINKAGE_HAVE_OFFSETS = 1
 ABI_VERSION = 12
 RANGE = 1000
 
@@ -144,6 +145,9 @@ PROTOTYPES = {
                                            c_void_p, c_i32, c_i32, c_void_p]),
     "gfm_hit_pairs": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_i32, c_i64, c_i64, c_i32, c_void_p, c_void_p, c_i64,
                               c_void_p, c_void_p, c_void_p, ctypes.c_uint32, P(c_i64), c_void_p]),
+    "gfm_hit_linkage": (c_int, [c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_i64, c_i32, c_i32, c_i64,
+                                c_double, c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i32, c_i32,
+                                ctypes.c_uint32, P(c_i64), c_void_p]),
     "gfm_region_labels": (c_i64, [ctypes.c_char_p, c_void_p, c_void_p, c_i64, c_void_p, c_i64]),
     "gfm_vcf_open": (c_int, [ctypes.c_char_p, ctypes.c_char_p, c_int, c_int, P(c_void_p), P(c_i64), P(c_i32),
                              P(c_i64)]),

@@ -21,6 +21,7 @@ cc -c "$here/graph_extract.hip" -o "$here/graph_extract.o"
 cc -c "$here/stream_calib.hip" -o "$here/stream_calib.o"
 cc -c "$here/region_reduce.hip" -o "$here/region_reduce.o"
 cc -c "$here/hit_pairs.hip" -o "$here/hit_pairs.o"
+cc -c "$here/hit_linkage.hip" -o "$here/hit_linkage.o"
 cc -c "$here/tsv_ingest.cpp" -o "$here/tsv_ingest.o"
 cc -c "$here/vcf_ingest.cpp" -o "$here/vcf_ingest.o"
 cc -c "$here/scan_stream.cpp" -o "$here/scan_stream.o"
@@ -30,6 +31,6 @@ cc -c "$here/hit_table.cpp" -o "$here/hit_table.o"
 cc -c "$here/variant_table.cpp" -o "$here/variant_table.o"
 for p in "${pids[@]}"; do wait "$p"; done
 "$HIPCC" --offload-arch=gfx950 -shared -fPIC -o "$here/libgrafimo_hip.so" \
-    "$here/grafimo_hip.o" "${quad[@]}" "$here/graph_extract.o" "$here/stream_calib.o" "$here/region_reduce.o" "$here/hit_pairs.o" "$here/tsv_ingest.o" \
+    "$here/grafimo_hip.o" "${quad[@]}" "$here/graph_extract.o" "$here/stream_calib.o" "$here/region_reduce.o" "$here/hit_pairs.o" "$here/hit_linkage.o" "$here/tsv_ingest.o" \
     "$here/vcf_ingest.o" "$here/scan_stream.o" "$here/gfm_workers.o" "$here/graph_tsv_writer.o" "$here/hit_table.o" "$here/variant_table.o" -lpthread -lz
 echo "built $here/libgrafimo_hip.so"

@@ -44,10 +44,11 @@ class HitAlleles:
     carrier_bits    uint64 [n, hw] or None;  haplotype_names [H] (empty for a graph without haplotypes);
     indexes         per chromosome entry its GraphIndex (None for an entry without regions);
     row_region      int64 [n] or None: the region listing of every row -- the index into the caller's flattened region list
-                    (entries in order, regions in order; a region listed twice is two listings)."""
+                    (entries in order, regions in order; a region listed twice is two listings);
+    row_entry       int64 [n] or None: the chromosome entry of every row (an index into `indexes`)."""
 
     def __init__(self, report: pd.DataFrame, allele_offsets, allele_entry, allele_site, allele, group_names, group_counts,
-                 carrier_bits, haplotype_names, indexes, *, row_region=None):
+                 carrier_bits, haplotype_names, indexes, *, row_region=None, row_entry=None):
         self.report = report
         self.allele_offsets = np.asarray(allele_offsets, dtype=np.int64)
         self.allele_entry = np.asarray(allele_entry, dtype=np.int32)
@@ -59,6 +60,7 @@ class HitAlleles:
         self.haplotype_names = list(haplotype_names)
         self.indexes = list(indexes)
         self.row_region = None if row_region is None else np.asarray(row_region, dtype=np.int64)
+        self.row_entry = None if row_entry is None else np.asarray(row_entry, dtype=np.int64)
 
     def __len__(self) -> int:
         return len(self.report)
@@ -237,7 +239,8 @@ def _report_order(spec) -> Tuple[np.ndarray, np.ndarray]:
 
 
 def _gather_rows(part, index, per_part, entry_of, recs, G: int, hw: int, want_masks: bool):
-    """the per-entry results of every graph handle into report order -> (offsets, entry, site, allele, group counts, masks)"""
+    """the per-entry results of every graph handle into report order -> (offsets, entry, site, allele, group counts, masks, the
+    rows' entries)"""
     n = len(part)
     lens = np.zeros(n, dtype=np.int64)
     first = np.zeros(n, dtype=np.int64)
@@ -266,7 +269,8 @@ def _gather_rows(part, index, per_part, entry_of, recs, G: int, hw: int, want_ma
     for gi, (_off, g_packed, _gc, _tot, _m) in enumerate(per_part):
         sel = p_of == gi
         packed[sel] = g_packed[src[sel]]
-    return (offsets, row_entry[row_of].astype(np.int32), (packed >> 2).astype(np.int32), (packed & 3).astype(np.uint8), gc, masks)
+    return (offsets, row_entry[row_of].astype(np.int32), (packed >> 2).astype(np.int32), (packed & 3).astype(np.uint8), gc, masks,
+            row_entry)
 
 
 def compute_hit_alleles_many(motifs: Sequence, graph, regions, debug: bool, args_obj, chrom_names=None,
@@ -337,7 +341,7 @@ def compute_hit_alleles_many(motifs: Sequence, graph, regions, debug: bool, args
                         for m, (part, index) in enumerate(orders)]
             frames = p.tables()
             for m, i in enumerate(idxs):
-                offsets, a_entry, a_site, a_allele, gc, masks = gathered[m]
+                offsets, a_entry, a_site, a_allele, gc, masks, row_entry = gathered[m]
                 if len(frames[m]) != len(offsets) - 1:
                     raise RuntimeError("the report and its order disagree on the number of rows")
                 part, index = orders[m]
@@ -347,7 +351,7 @@ def compute_hit_alleles_many(motifs: Sequence, graph, regions, debug: bool, args
                     if len(rows):
                         row_region[rows] = listing_of[gi][p.got[m][gi][3]["region"][index[rows]]]
                 out[i] = HitAlleles(frames[m], offsets, a_entry, a_site, a_allele, group_names, gc, masks, names, indexes,
-                                    row_region=row_region)
+                                    row_region=row_region, row_entry=row_entry)
         finally:
             p.close()
     return out

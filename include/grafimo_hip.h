@@ -688,6 +688,33 @@ int gfm_hit_pairs(const int32_t *d_group, const int64_t *d_lo, const int64_t *d_
                   int64_t *d_pair_off, int64_t pair_capacity, int32_t *d_pair_b, int32_t *d_joint, int32_t *d_group_counts,
                   uint32_t flags, int64_t *h_total, void *stream);
 
+/* ------------------------------------------------------------------ hit linkage: alleles in LD with a row's carriers
+ * Graph-independent (csrc/hit_linkage.hip).  n_rows rows (< 2^31 - 1) in device memory in ascending d_lo order: d_lo <= d_hi
+ * int64 (|x| < 2^61), d_masks uint64 [n_rows][hw]; n_sites sites (< 2^29) in ascending d_pos order (equal positions allowed):
+ * d_pos int64, d_n_alts uint8 (<= 3), d_allele_bits uint64 [n_sites][3][hw] -- the slots a > n_alts are ignored whatever they
+ * hold.  hw = ceil(n_haplotypes / 64), 1 <= n_haplotypes <= 32 768; the bits beyond n_haplotypes are CLEAR in the masks and the
+ * used slots: the library does not mask them.  A cell (row, site, allele a = 1 .. n_alts) is a candidate when
+ * max(lo - pos, pos - (hi - 1), 0) <= flank (0 <= flank < 2^61).  With n_hit = popcount(mask), n_allele = popcount(slot),
+ * n_joint = popcount(mask & slot), H = n_haplotypes:  Dn = H n_joint - n_hit n_allele,
+ * den = n_hit (H - n_hit) n_allele (H - n_allele), both exact in int64.  A candidate is LISTED when den != 0 and, in fp64,
+ * Dn^2 >= (min_r2 - 1e-9) den (0 <= min_r2 <= 1): r^2 >= min_r2 with slack -- the caller computes r^2 from the integers and
+ * makes the exact cut; the device's rounding can only list a cell too many.  The result is a CSR over the rows:
+ *   d_link_off int64 [n_rows + 1]: the links of row i are d_link_off[i] .. d_link_off[i + 1] - 1; *h_total = d_link_off[n_rows];
+ *   d_site int32, d_allele uint8 (1 .. 3), d_joint int32 [link_capacity]: ascending (site, allele) within a row;
+ *   d_n_hit int32 [n_rows];  d_n_allele int32 [n_sites][3] (0 in the unused slots): written by every call.
+ * Count first, then allocate: the link arrays are written only when link_capacity >= *h_total (else they are untouched and
+ * may be NULL with link_capacity 0).  GFM_LINKAGE_HAVE_OFFSETS: d_link_off already holds the offsets an earlier call made for
+ * the same input, the counting pass is not run again.  rows_per_tile (0: 32; 8, 16 or 32) and slots_per_chunk (0: 256; 64,
+ * 128 or 256) cut the work; the result does not depend on them; other values give GFM_ERR_INVALID.  The input is CHECKED on
+ * the device before anything is counted: rows or sites out of order, lo > hi, n_alts > 3 or a coordinate beyond the limit
+ * give GFM_ERR_INVALID and no link.  The call WAITS for the stream (it reads the verdict of the check and the total). */
+#define GFM_LINKAGE_HAVE_OFFSETS 1u
+int gfm_hit_linkage(const int64_t *d_lo, const int64_t *d_hi, const uint64_t *d_masks, int64_t n_rows, const int64_t *d_pos,
+                    const uint8_t *d_n_alts, const uint64_t *d_allele_bits, int64_t n_sites, int32_t hw, int32_t n_haplotypes,
+                    int64_t flank, double min_r2, int64_t *d_link_off, int64_t link_capacity, int32_t *d_site,
+                    uint8_t *d_allele, int32_t *d_joint, int32_t *d_n_hit, int32_t *d_n_allele, int32_t rows_per_tile,
+                    int32_t slots_per_chunk, uint32_t flags, int64_t *h_total, void *stream);
+
 /* Phased VCF (plain or gzip/bgzip) -> the site arrays of gfm_graph_create for one chromosome; host
  * threads parse the lines.  The reference hands the VCF to `vg construct` / `vg index -G`
  * (constructVG.py:332,394); here every ALT allele is taken apart: single-base substitutions (one site per
