@@ -1445,62 +1445,54 @@ graph_hist_reduce_kernel(const unsigned *__restrict__ slabs, int n_slabs, int sl
     if (sum) atomicAdd(&hist[b < hnb ? hlo + b : min_val], sum);
 }
 
+// word `word` of a walk's carrier set: the AND of allele_word over its n constraints (at(k, site, allele)), the bits beyond
+// n_hap cleared.  STOP: leave at the first zero -- a loop over words that wants each answer before it goes on; without it
+// the loads of all of a lane's constraints are in flight together.
+template <bool STOP, class F>
+__device__ __forceinline__ unsigned long long carrier_word(const GraphDev &g, int n, F at, int word)
+{
+    unsigned long long acc = ~0ull;
+    if (word == g.hw - 1 && (g.n_hap & 63)) acc = (1ull << (g.n_hap & 63)) - 1ull;
+    for (int k = 0; k < n && (!STOP || acc); ++k) {
+        int site, al;
+        at(k, site, al);
+        acc &= allele_word(g, site, al, word);
+    }
+    return acc;
+}
+
 // the AND of the bitsets by a whole wavefront: lane per word (80 words for 5 096 haplotypes), all of a lane's loads in
 // flight together, wave sum -- every lane returns the count.  (One thread per hit walked the words sixteen at a time:
 // tens of microseconds for a walk through six constraint sites, and the kernel is as slow as its slowest hit.)
 template <class F>
 __device__ inline long long count_by_bitsets_wave(const GraphDev &g, int n, F at)
 {
-    const int lane = threadIdx.x & 63;
     long long count = 0;
-    for (int word = lane; word < g.hw; word += 64) {
-        unsigned long long acc = ~0ull;
-        if (word == g.hw - 1 && (g.n_hap & 63)) acc = (1ull << (g.n_hap & 63)) - 1ull;
-        for (int k = 0; k < n; ++k) {
-            int site, al;
-            at(k, site, al);
-            acc &= allele_word(g, site, al, word);
-        }
-        count += __popcll(acc);
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const int lo_ = __shfl_xor((int)(count & 0xffffffffll), off), hi_ = __shfl_xor((int)(count >> 32), off);
-        count += ((long long)hi_ << 32) | (unsigned)lo_;
-    }
-    return count;
+    for (int word = threadIdx.x & 63; word < g.hw; word += 64) count += __popcll(carrier_word<false>(g, n, at, word));
+    return wave_sum_ll(count);
 }
 
-// ---- the columns of the hit rows.  WAVEFRONT per hit: every lane follows the same path -- tile and window from the
-// entry, then what the materialising emit kernels do for every row: for a plain window the mixed-radix digits, the
-// bases, the count from the tables; for a listed window the odometer up to the walk's rank and one replay with the
-// visitor that collects the haplotype constraints -- so the chain of loads is one wavefront's, not sixty-four divergent
-// threads', and where the count needs the bitsets the lanes share the words.  Lane 0 writes the record.
-__device__ __forceinline__ void annotate_hit(const GraphDev &g, const int *__restrict__ allele_count, int W,
-                                             const Tile *__restrict__ tiles, int n_tiles, const GraphHit *__restrict__ hits,
-                                             const int *__restrict__ d_cutoff, const double *__restrict__ qtable,
-                                             HitRec *__restrict__ out, long long hi_)
+__device__ __forceinline__ const Tile &hit_tile(const Tile *__restrict__ tiles, int n_tiles, const GraphHit &h)
 {
-    const bool writer = threadIdx.x == 0;
-    const GraphHit hit = hits[hi_];
-    const Tile t = tiles[min(max(hit.tile, 0), n_tiles - 1)];
+    return tiles[min(max(h.tile, 0), n_tiles - 1)];
+}
+
+// ---- the walk of one hit entry, re-derived.  WAVEFRONT per entry: every lane follows the same path -- window of the tile
+// and walk number from the entry, the tile's site records staged, then what the materialising emit kernels do for every
+// row: for a plain window the mixed-radix digits; for a listed window the odometer up to the walk's rank and one replay
+// with the visitor that collects the haplotype constraints, plus the deletions that cover the window's first base -- so
+// the chain of loads is one wavefront's, not sixty-four divergent threads'.  Calls f(n, at, end, any_alt) ONCE: the walk's
+// n constraints through at(k, site, allele), the position behind its last base, whether it takes an alternate allele; `at`
+// is the digit accessor or the DelEmit one, so f is compiled for each.  BASES: the walk's W bases into km as well
+// (km: 2 * GFM_MAX_WIDTH bytes of the caller's; else unused).  -> false: no such walk (cannot happen: the score kernel
+// found it), f was not called.  graph_annotate_kernel, hh_mask_kernel and ha_entry_kernel are built on it; their
+// barrier between two entries is what lets the LDS here be written again.
+template <bool BASES, class F>
+__device__ __forceinline__ bool hit_walk(const GraphDev &g, int W, const Tile &t, const GraphHit &hit, uint8_t *km, F f)
+{
     const int k = (int)(hit.q2k >> kHitWinShift) & 0xff;
-    const long long q2 = hit.q2k & kHitWalkMask;
-    HitRec rec{};
-    rec.w = t.w_base + k;
-    rec.score = hit.score;
-    rec.q2 = q2;
-    rec.keep = (!d_cutoff || hit.score >= *d_cutoff) ? 1 : 0;
-    rec.qvalue = qtable ? qtable[hit.score] : 0.0;
+    const long long q = (hit.q2k & kHitWalkMask) >> 1;
     const long long p = t.p0 + k;
-    const long long q = q2 >> 1;
-    const bool minus = (q2 & 1) != 0;
-    rec.region = t.region;
-    rec.strand = minus ? '-' : '+';
-    if (!rec.keep) { if (writer) out[hi_] = rec; return; }          // a p < t candidate that the q-value cutoff drops
-    uint8_t km[2 * GFM_MAX_WIDTH];
-    long long end_pos = p + W, count = 0;
-    bool any_alt = false;
     // the tile's site records into LDS in one go, as graph_score_kernel stages them: the window's first site is a search, and
     // through global memory that was seven dependent round trips before anything else could start
     __shared__ SiteRec a_rec[kWaveSites];
@@ -1515,7 +1507,7 @@ __device__ __forceinline__ void annotate_hit(const GraphDev &g, const int *__res
     __syncthreads();
     const WinInfo wi = classify_window(g, TileSites{g, a_rec, a_reach, t.p0, t.i_lo, staged}, p, W, t.limit, t.i_lo, t.i_hi);
     if (!wi.listed) {
-        {
+        if constexpr (BASES) {
             unsigned long long rw[8];
 #pragma unroll
             for (int c = 0; c < 8; ++c) rw[c] = 8 * c < W ? load_u64(g.ref + p + 8 * c) : 0ull;
@@ -1529,53 +1521,86 @@ __device__ __forceinline__ void annotate_hit(const GraphDev &g, const int *__res
             const int nall = 1 + g.n_alts[wi.i0 + s_];
             const unsigned long long al = (unsigned long long)take_digit(rest, nall);
             dig[s_ >> 5] |= al << (2 * (s_ & 31));
-            if (al) km[g.pos[wi.i0 + s_] - p] = g.alt_bases[(size_t)(wi.i0 + s_) * kMaxAlts + (al - 1)];
+            if constexpr (BASES)
+                if (al) km[g.pos[wi.i0 + s_] - p] = g.alt_bases[(size_t)(wi.i0 + s_) * kMaxAlts + (al - 1)];
         }
-        any_alt = (dig[0] | dig[1]) != 0ull;
-        auto at = [&](int kk, int &site, int &al) { site = wi.i0 + kk; al = (int)((dig[kk >> 5] >> (2 * (kk & 31))) & 3ull); };
-        bool done;
-        count = count_by_tables(g, allele_count, wi.ns, at, done);
-        if (!done) count = count_by_bitsets_wave(g, wi.ns, at);
-    } else {
-        // the window's first site records in LDS, in one batch: the odometer below is a chain of "what is at x" questions
-        __shared__ SiteRec ann_cache[kSiteCache];
-        if (threadIdx.x < kSiteCache) ann_cache[threadIdx.x] = g.site_rec[wi.i0 + threadIdx.x];
-        __syncthreads();
-        const CachedSites cs{g.site_rec, ann_cache, wi.i0, 1};
-        WalkState st;
-        WalkStart ws;
-        NoVisitor nv;
-        long long rest = q, prod = 0;
-        bool found = false, more = true;
-        while (!found && more) {
-            int prefix = 0;
-            for (;;) {
-                const int rc = simulate<NoVisitor, CachedSites, kFusedMaxWalks>(g, cs, p, W, wi.i0, ws, prefix, st, nv, 0, 0, prod, t.limit);
-                if (rc == WALK_OK) {
-                    if (rest < prod) { found = true; break; }
-                    rest -= prod;
-                }
-                prefix = next_walk(st);
-                if (prefix < 0) break;
+        f(wi.ns, [&](int kk, int &site, int &al) { site = wi.i0 + kk; al = (int)((dig[kk >> 5] >> (2 * (kk & 31))) & 3ull); },
+          p + W, (dig[0] | dig[1]) != 0ull);
+        return true;
+    }
+    // the window's first site records in LDS, in one batch: the odometer below is a chain of "what is at x" questions
+    __shared__ SiteRec ann_cache[kSiteCache];
+    if (threadIdx.x < kSiteCache) ann_cache[threadIdx.x] = g.site_rec[wi.i0 + threadIdx.x];
+    __syncthreads();
+    const CachedSites cs{g.site_rec, ann_cache, wi.i0, 1};
+    WalkState st;
+    WalkStart ws;
+    NoVisitor nv;
+    long long rest = q, prod = 0;
+    bool found = false, more = true;
+    while (!found && more) {
+        int prefix = 0;
+        for (;;) {
+            const int rc = simulate<NoVisitor, CachedSites, kFusedMaxWalks>(g, cs, p, W, wi.i0, ws, prefix, st, nv, 0, 0, prod, t.limit);
+            if (rc == WALK_OK) {
+                if (rest < prod) { found = true; break; }
+                rest -= prod;
             }
-            if (!found) more = next_start(g, p, wi.i0, ws);
+            prefix = next_walk(st);
+            if (prefix < 0) break;
         }
-        if (!found) { rec.keep = 0; if (writer) out[hi_] = rec; return; }      // cannot happen: the score kernel found this walk
-        int src[GFM_MAX_WIDTH];
-        int more_cons[kMaxConstraints - 4];
-        DelEmit em(g, km, km + W, src, W, more_cons);
-        long long again = 0;
-        simulate<DelEmit, CachedSites, kFusedMaxWalks>(g, cs, p, W, wi.i0, ws, st.nd, st, em, rest, prod, again, t.limit);
+        if (!found) more = next_start(g, p, wi.i0, ws);
+    }
+    if (!found) return false;
+    uint8_t own[BASES ? 1 : 2 * GFM_MAX_WIDTH];          // (the visitor writes the bases somewhere)
+    uint8_t *kb = BASES ? km : own;
+    int src[GFM_MAX_WIDTH];
+    int more_cons[kMaxConstraints - 4];
+    DelEmit em(g, kb, kb + W, src, W, more_cons);
+    long long again = 0;
+    simulate<DelEmit, CachedSites, kFusedMaxWalks>(g, cs, p, W, wi.i0, ws, st.nd, st, em, rest, prod, again, t.limit);
+    if constexpr (BASES)
         for (int j = 0; j < W; ++j)
             if (src[j] >= 0) km[j] = g.ref[src[j]];
-        if (!(ws.site >= 0 && st.last == p - 1)) for_covering_deletions(g, p, wi.i0, [&](int dsite) { em.add(dsite, 0); });
-        auto at = [&](int kk, int &site, int &al) { const int v = em.get(kk); site = v >> 4; al = v & 3; };
+    if (!(ws.site >= 0 && st.last == p - 1)) for_covering_deletions(g, p, wi.i0, [&](int dsite) { em.add(dsite, 0); });
+    f(em.n_cons, [&](int kk, int &site, int &al) { const int v = em.get(kk); site = v >> 4; al = v & 3; }, st.last + 1, em.alt);
+    return true;
+}
+
+// ---- the columns of the hit rows: the walk's bases, its end, vg's ref flag, and the haplotype count -- from the tables,
+// and where those cannot answer from the bitsets, whose words the lanes share.  Lane 0 writes the record.
+__device__ __forceinline__ void annotate_hit(const GraphDev &g, const int *__restrict__ allele_count, int W,
+                                             const Tile *__restrict__ tiles, int n_tiles, const GraphHit *__restrict__ hits,
+                                             const int *__restrict__ d_cutoff, const double *__restrict__ qtable,
+                                             HitRec *__restrict__ out, long long hi_)
+{
+    const bool writer = threadIdx.x == 0;
+    const GraphHit hit = hits[hi_];
+    const Tile t = hit_tile(tiles, n_tiles, hit);
+    const int k = (int)(hit.q2k >> kHitWinShift) & 0xff;
+    const long long q2 = hit.q2k & kHitWalkMask;
+    HitRec rec{};
+    rec.w = t.w_base + k;
+    rec.score = hit.score;
+    rec.q2 = q2;
+    rec.keep = (!d_cutoff || hit.score >= *d_cutoff) ? 1 : 0;
+    rec.qvalue = qtable ? qtable[hit.score] : 0.0;
+    const long long p = t.p0 + k;
+    const bool minus = (q2 & 1) != 0;
+    rec.region = t.region;
+    rec.strand = minus ? '-' : '+';
+    if (!rec.keep) { if (writer) out[hi_] = rec; return; }          // a p < t candidate that the q-value cutoff drops
+    uint8_t km[2 * GFM_MAX_WIDTH];
+    long long end_pos = 0, count = 0;
+    bool any_alt = false;
+    const bool found = hit_walk<true>(g, W, t, hit, km, [&](int n, auto at, long long end, bool alt) {
         bool done;
-        count = count_by_tables(g, allele_count, em.n_cons, at, done);
-        if (!done) count = count_by_bitsets_wave(g, em.n_cons, at);
-        end_pos = st.last + 1;
-        any_alt = em.alt;
-    }
+        count = count_by_tables(g, allele_count, n, at, done);
+        if (!done) count = count_by_bitsets_wave(g, n, at);
+        end_pos = end;
+        any_alt = alt;
+    });
+    if (!found) { rec.keep = 0; if (writer) out[hi_] = rec; return; }
     if (!writer) return;
     rec.freq = count;
     rec.is_ref = any_alt ? 0 : 1;

@@ -1,8 +1,7 @@
 // gfm_graph_haplotypes.hpp -- the per-haplotype hit matrix: for every region of the last fused scoring call and every
 // haplotype of the graph, how many of the region's hit rows the haplotype carries and the best (highest) scaled score among
 // them.  (Included at the end of graph_extract.hip: it reads the hit entries of gfm_graph_score[_multi] and the plan's tile
-// table, and walks the graph with the machinery graph_annotate_kernel uses -- classify_window, simulate(), DelEmit,
-// for_covering_deletions, allele_word.)
+// table, and re-derives their walks with the function graph_annotate_kernel uses: hit_walk.)
 //
 // A haplotype CARRIES a row when it is in the set whose size is the row's haplotype_frequency: the AND of the bitsets of
 // the walk's allele constraints.  graph_annotate_kernel keeps only the popcount of that set; here the set itself is kept.
@@ -11,7 +10,7 @@
 //   1. hh_region_count_kernel / hh_scatter_kernel: the entries that pass the cutoff grouped by region -- a count per
 //      region, an exclusive scan (hipcub), a scatter of entry indices (order inside a region is arbitrary).
 //   2. per batch of the grouped entries whose masks fit the scratch budget:
-//      hh_mask_kernel -- a WAVEFRONT per entry re-derives the walk's constraints as annotate_hit does and its lanes write
+//      hh_mask_kernel -- a WAVEFRONT per entry re-derives the walk's constraints (hit_walk) and its lanes write
 //      the AND of the bitsets, a 64-bit word per lane, the tail bits beyond n_hap cleared;
 //      hh_reduce_kernel -- a workgroup per (region, 256 haplotypes), a thread per haplotype: over the region's entries of the
 //      batch the 64 lanes of a wave read the SAME mask word (a broadcast load), test their bit, count and take the maximum
@@ -28,7 +27,7 @@ __device__ __forceinline__ bool hh_kept(const GraphHit &h, const int *d_cutoff) 
 
 __device__ __forceinline__ int hh_region(const Tile *__restrict__ tiles, int n_tiles, const GraphHit &h)
 {
-    return tiles[min(max(h.tile, 0), n_tiles - 1)].region;
+    return hit_tile(tiles, n_tiles, h).region;
 }
 
 // cnt[r] += entries of region r that pass the cutoff (--qvalueT; none: all of them, as in annotate)
@@ -61,89 +60,17 @@ hh_scatter_kernel(const Tile *__restrict__ tiles, int n_tiles, const GraphHit *_
     }
 }
 
-// the AND of the bitsets by a whole wavefront, stored: count_by_bitsets_wave keeping `acc` instead of its popcount
-template <class F>
-__device__ inline void and_bitsets_wave(const GraphDev &g, int n, F at, unsigned long long *__restrict__ out)
-{
-    for (int word = threadIdx.x & 63; word < g.hw; word += 64) {
-        unsigned long long acc = ~0ull;
-        if (word == g.hw - 1 && (g.n_hap & 63)) acc = (1ull << (g.n_hap & 63)) - 1ull;
-        for (int k = 0; k < n && acc; ++k) {
-            int site, al;
-            at(k, site, al);
-            acc &= allele_word(g, site, al, word);
-        }
-        out[word] = acc;
-    }
-}
-
-// The carrier set of one hit entry: the walk's constraints exactly as annotate_hit derives them (plain window: the
-// mixed-radix digits of the walk number; listed window: the layout odometer up to the walk's rank, one replay with DelEmit,
-// the deletions that cover the window's first base), then the AND of their bitsets into out[0 .. hw).
+// The carrier set of one hit entry into out[0 .. hw): the AND of the bitsets of the walk's constraints (hit_walk), a word
+// per lane -- count_by_bitsets_wave keeping the words instead of their popcounts.  No such walk: no carriers.
 __device__ __forceinline__ void hh_mask_hit(const GraphDev &g, int W, const Tile *__restrict__ tiles, int n_tiles,
                                             const GraphHit &hit, unsigned long long *__restrict__ out)
 {
-    const Tile t = tiles[min(max(hit.tile, 0), n_tiles - 1)];
-    const int k = (int)(hit.q2k >> kHitWinShift) & 0xff;
-    const long long q = (hit.q2k & kHitWalkMask) >> 1;
-    const long long p = t.p0 + k;
-    __shared__ SiteRec a_rec[kWaveSites];
-    __shared__ int a_reach[kWaveSites];
-    const int staged = min(t.i_far - t.i_lo + 1, kWaveSites);
-    for (int s_ = threadIdx.x; s_ < staged; s_ += 64) {
-        const int i = t.i_lo + s_;
-        a_rec[s_] = packed_site(g, i);
-        const long long r = (i <= g.n_sites ? g.max_reach[i] : -1ll) - t.p0;
-        a_reach[s_] = (int)max(-1ll, min(r, 0x7fffffffll));
-    }
-    __syncthreads();
-    const WinInfo wi = classify_window(g, TileSites{g, a_rec, a_reach, t.p0, t.i_lo, staged}, p, W, t.limit, t.i_lo, t.i_hi);
-    if (!wi.listed) {
-        unsigned long long dig[2] = {0ull, 0ull};
-        unsigned long long rest = (unsigned long long)q;
-        for (int s_ = wi.ns - 1; s_ >= 0; --s_) {
-            const int nall = 1 + g.n_alts[wi.i0 + s_];
-            dig[s_ >> 5] |= (unsigned long long)take_digit(rest, nall) << (2 * (s_ & 31));
-        }
-        auto at = [&](int kk, int &site, int &al) { site = wi.i0 + kk; al = (int)((dig[kk >> 5] >> (2 * (kk & 31))) & 3ull); };
-        and_bitsets_wave(g, wi.ns, at, out);
-        return;
-    }
-    __shared__ SiteRec ann_cache[kSiteCache];
-    if (threadIdx.x < kSiteCache) ann_cache[threadIdx.x] = g.site_rec[wi.i0 + threadIdx.x];
-    __syncthreads();
-    const CachedSites cs{g.site_rec, ann_cache, wi.i0, 1};
-    WalkState st;
-    WalkStart ws;
-    NoVisitor nv;
-    long long rest = q, prod = 0;
-    bool found = false, more = true;
-    while (!found && more) {
-        int prefix = 0;
-        for (;;) {
-            const int rc = simulate<NoVisitor, CachedSites, kFusedMaxWalks>(g, cs, p, W, wi.i0, ws, prefix, st, nv, 0, 0, prod, t.limit);
-            if (rc == WALK_OK) {
-                if (rest < prod) { found = true; break; }
-                rest -= prod;
-            }
-            prefix = next_walk(st);
-            if (prefix < 0) break;
-        }
-        if (!found) more = next_start(g, p, wi.i0, ws);
-    }
-    if (!found) {                                  // cannot happen (the score kernel found this walk): no carriers
+    const Tile t = hit_tile(tiles, n_tiles, hit);
+    const bool found = hit_walk<false>(g, W, t, hit, nullptr, [&](int n, auto at, long long, bool) {
+        for (int word = threadIdx.x & 63; word < g.hw; word += 64) out[word] = carrier_word<true>(g, n, at, word);
+    });
+    if (!found)
         for (int word = threadIdx.x; word < g.hw; word += 64) out[word] = 0ull;
-        return;
-    }
-    uint8_t km[2 * GFM_MAX_WIDTH];
-    int src[GFM_MAX_WIDTH];
-    int more_cons[kMaxConstraints - 4];
-    DelEmit em(g, km, km + W, src, W, more_cons);
-    long long again = 0;
-    simulate<DelEmit, CachedSites, kFusedMaxWalks>(g, cs, p, W, wi.i0, ws, st.nd, st, em, rest, prod, again, t.limit);
-    if (!(ws.site >= 0 && st.last == p - 1)) for_covering_deletions(g, p, wi.i0, [&](int dsite) { em.add(dsite, 0); });
-    auto at = [&](int kk, int &site, int &al) { const int v = em.get(kk); site = v >> 4; al = v & 3; };
-    and_bitsets_wave(g, em.n_cons, at, out);
 }
 
 // a wavefront per grouped entry i in [b0, min(b1, kept)): its mask into masks[i - b0][hw], its score into bscore[i - b0]
@@ -186,26 +113,19 @@ hh_reduce_kernel(const unsigned long long *__restrict__ masks, const int *__rest
     }
 }
 
-inline size_t hh_align(size_t b) { return (b + 255) & ~(size_t)255; }
-
 }  // namespace
 
 GFM_API int gfm_graph_haplotype_hits(gfm_graph_t g, const void *d_hits, const uint64_t *d_hit_count, int64_t hit_capacity,
                                      const int32_t *d_cutoff, int32_t n_regions, int32_t *d_counts, int32_t *d_best,
                                      int64_t scratch_bytes, void *stream)
 {
-    if (!g) return gfail(GFM_ERR_INVALID, "graph is NULL");
-    if (!g->dev.alt_bits || g->dev.n_hap <= 0)
-        return gfail(GFM_ERR_INVALID, "gfm_graph_haplotype_hits: the graph carries no haplotypes (no bitsets were given to "
-                                      "gfm_graph_create: an XG without its GBWT, or a VCF without samples)");
+    if (const int rc = check_hit_list(g, "gfm_graph_haplotype_hits", d_hits, d_hit_count, hit_capacity)) return rc;
+    if (!has_haplotypes(*g)) return fail_no_haplotypes("gfm_graph_haplotype_hits");
     FusedPlan *P = g->plan;
-    if (!P) return gfail(GFM_ERR_INVALID, "gfm_graph_haplotype_hits: no gfm_graph_score call on this handle");
     if (n_regions < 0 || (size_t)n_regions != P->f_starts.size())
         return gfail(GFM_ERR_INVALID, "gfm_graph_haplotype_hits: n_regions = " + std::to_string(n_regions) + " but the last "
                                       "gfm_graph_score call had " + std::to_string(P->f_starts.size()) + " regions");
-    if ((n_regions && (!d_counts || !d_best)) || hit_capacity < 0) return gfail(GFM_ERR_INVALID, "bad argument");
-    if (hit_capacity > 0 && (!d_hits || !d_hit_count)) return gfail(GFM_ERR_INVALID, "NULL device buffer");
-    if (hit_capacity > 0x7fffffffll) return gfail(GFM_ERR_INVALID, "hit capacity beyond 2^31");
+    if (n_regions && (!d_counts || !d_best)) return gfail(GFM_ERR_INVALID, "bad argument");
     const hipStream_t st = static_cast<hipStream_t>(stream);
     const int H = g->dev.n_hap, hw = g->dev.hw;
     const size_t cells = (size_t)n_regions * (size_t)H;
@@ -222,11 +142,11 @@ GFM_API int gfm_graph_haplotype_hits(gfm_graph_t g, const void *d_hits, const ui
     size_t cub_bytes = 0;
     GX_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, cub_bytes, static_cast<int *>(nullptr), static_cast<int *>(nullptr),
                                             n_regions + 1, st));
-    const size_t b_cnt = hh_align(sizeof(int) * ((size_t)n_regions + 1));
-    const size_t b_perm = hh_align(sizeof(int) * (size_t)hit_capacity);
-    const size_t b_score = hh_align(sizeof(int) * (size_t)batch);
-    const size_t b_mask = hh_align(sizeof(unsigned long long) * (size_t)batch * (size_t)hw);
-    const size_t total = 2 * b_cnt + b_perm + b_score + b_mask + hh_align(cub_bytes);
+    const size_t b_cnt = align256(sizeof(int) * ((size_t)n_regions + 1));
+    const size_t b_perm = align256(sizeof(int) * (size_t)hit_capacity);
+    const size_t b_score = align256(sizeof(int) * (size_t)batch);
+    const size_t b_mask = align256(sizeof(unsigned long long) * (size_t)batch * (size_t)hw);
+    const size_t total = 2 * b_cnt + b_perm + b_score + b_mask + align256(cub_bytes);
     unsigned char *base = nullptr;
     GX_TRY(hipMallocAsync(reinterpret_cast<void **>(&base), total, st));
     int *cnt = reinterpret_cast<int *>(base);

@@ -1,7 +1,7 @@
 // gfm_graph_hapscores.hpp -- the per-haplotype best motif score: for every region of the caller's list and every haplotype
 // of the graph, the highest-scoring k-mer of the haplotype's own sequence in the region, with no threshold and no hit list
-// (included at the end of graph_extract.hip: it walks the graph with the machinery graph_variant_kernel uses -- simulate(),
-// DelEmit, for_covering_deletions, allele_word -- and scores with the motif's packed two-strand table of the fused path).
+// (included at the end of graph_extract.hip: it enumerates a window's walks as graph_variant_kernel does --
+// for_window_layouts, replay_walk -- and scores with the motif's packed two-strand table of the fused path).
 //
 // Rows(r, h) are the report's threshold-1 rows of region r whose walk haplotype h CARRIES (h is in the AND of the bitsets of
 // the walk's allele constraints, the set whose popcount is haplotype_frequency).  The best row is the one with the largest
@@ -69,11 +69,8 @@ __device__ inline void hs_carriers(const GraphDev &g, int w0, int nw, int n_rec,
             const int hl = w * 64 + lane;
             const unsigned long long cur = keys_lds[hl];        // (may be stale: the atomic settles it)
             if (!__builtin_amdgcn_ballot_w64(key > cur)) continue;
-            unsigned long long acc = ~0ull;
-            for (int c = 0; c < n && acc; ++c) {
-                const int v = pool[off + c];
-                acc &= allele_word(g, v >> 4, v & 3, w0 + w);
-            }
+            auto at = [&](int c, int &site, int &al) { const int v = pool[off + c]; site = v >> 4; al = v & 3; };
+            const unsigned long long acc = carrier_word<true>(g, n, at, w0 + w);
             if (((acc >> lane) & 1ull) && key > cur) atomicMax(&keys_lds[hl], key);
         }
     }
@@ -125,80 +122,57 @@ graph_hapscore_kernel(GraphDev g, const unsigned *__restrict__ ftab, int W, int 
             if (plain_win[k]) continue;
             const long long p = run.p0 + k;
             const int i0 = lower_bound_pos(g.pos, g.n_sites, p);
-            const GlobalSites sites{g.site_rec};
-            WalkStart ws;
-            long long total = 0;
-            bool over = false;
-            for (;;) {                                     // the starts: plain, then inside insertions anchored at p - 1
-                WalkState st;
-                NoVisitor nv;
-                int prefix = 0;
-                for (;;) {                                 // the layouts of this start (uniform over the wave)
-                    long long prod = 0;
-                    const int rc = simulate<NoVisitor, GlobalSites, kHsMaxWalks>(g, sites, p, W, i0, ws, prefix, st, nv, 0, 0, prod,
-                                                                                 run.limit);
-                    if (rc == WALK_OVERFLOW) { over = true; break; }
-                    if (rc == WALK_OK) {
-                        total += prod;
-                        if (total > kHsMaxWalks) { over = true; break; }
-                        for (long long q0 = 0; q0 < prod; q0 += 64) {
-                            const long long q = q0 + lane;
-                            uint8_t km[GFM_MAX_WIDTH], kr[GFM_MAX_WIDTH];
-                            int src[GFM_MAX_WIDTH];
-                            int more[kMaxConstraints - 4];
-                            DelEmit em(g, km, kr, src, W, more);
-                            int nc = 0;                     // constraints this lane queues
-                            unsigned long long key = 0ull;
-                            if (q < prod) {
-                                WalkState s2 = st;
-                                long long again = 0;
-                                simulate<DelEmit, GlobalSites, kHsMaxWalks>(g, sites, p, W, i0, ws, st.nd, s2, em, q, prod, again,
-                                                                            run.limit);
-                                if (!(ws.site >= 0 && s2.last == p - 1)) for_covering_deletions(g, p, i0, [&](int d) { em.add(d, 0); });
-                                unsigned sum = 0u;
-                                int bad = 0;
-                                for (int j = 0; j < W; ++j) {
-                                    const unsigned c = base_code(src[j] >= 0 ? g.ref[src[j]] : km[j]);
-                                    sum += ftab[j * 8 + (c & 7u)];
-                                    bad |= (int)(c >> 2);
-                                }
-                                key = hs_walk_key(sum, bad, min_val, p, s2.last + 1, forward_only, run.base);
-                                bool ref = true;
-                                for (int c = 0; c < em.n_cons; ++c)
-                                    if (em.get(c) & 3) ref = false;
-                                if (em.n_cons == 0) all_k = key > all_k ? key : all_k;       // a walk over no site: everyone's
-                                else nc = em.n_cons;
-                                if (ref) ref_k = key > ref_k ? key : ref_k;
-                            }
-                            // queue the records (in pieces that fit the pool) and run the carrier pass over them
-                            const int incl = wave_prefix_sum(nc), ex = incl - nc;
-                            const int total_c = __shfl(incl, 63);
-                            for (int done = 0; done < total_c;) {
-                                const bool mine = nc > 0 && ex >= done && incl <= done + kHsPool;
-                                const unsigned long long bal = __builtin_amdgcn_ballot_w64(mine);
-                                if (mine) {
-                                    const int slot = __popcll(bal & ((1ull << lane) - 1ull));
-                                    q_key[wave][slot] = key;
-                                    q_off[wave][slot] = ex - done;
-                                    q_n[wave][slot] = nc;
-                                    for (int c = 0; c < nc; ++c) q_pool[wave][ex - done + c] = em.get(c);
-                                }
-                                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                                __builtin_amdgcn_wave_barrier();
-                                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-                                hs_carriers(g, w0, nw, __popcll(bal), q_key[wave], q_off[wave], q_n[wave], q_pool[wave], hs_keys);
-                                done = __shfl(incl, 63 - __clzll(bal));
-                                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                                __builtin_amdgcn_wave_barrier();
-                                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-                            }
+            const bool over = for_window_layouts<kHsMaxWalks>(g, p, W, i0, run.limit, [&](const WalkStart &ws, const WalkState &st,
+                                                                                          long long prod) {
+                for (long long q0 = 0; q0 < prod; q0 += 64) {
+                    const long long q = q0 + lane;
+                    uint8_t km[GFM_MAX_WIDTH], kr[GFM_MAX_WIDTH];
+                    int src[GFM_MAX_WIDTH];
+                    int more[kMaxConstraints - 4];
+                    DelEmit em(g, km, kr, src, W, more);
+                    int nc = 0;                     // constraints this lane queues
+                    unsigned long long key = 0ull;
+                    if (q < prod) {
+                        const long long end = replay_walk<kHsMaxWalks>(g, p, W, i0, ws, st, q, prod, run.limit, em);
+                        unsigned sum = 0u;
+                        int bad = 0;
+                        for (int j = 0; j < W; ++j) {
+                            const unsigned c = base_code(src[j] >= 0 ? g.ref[src[j]] : km[j]);
+                            sum += ftab[j * 8 + (c & 7u)];
+                            bad |= (int)(c >> 2);
                         }
+                        key = hs_walk_key(sum, bad, min_val, p, end, forward_only, run.base);
+                        bool ref = true;
+                        for (int c = 0; c < em.n_cons; ++c)
+                            if (em.get(c) & 3) ref = false;
+                        if (em.n_cons == 0) all_k = key > all_k ? key : all_k;       // a walk over no site: everyone's
+                        else nc = em.n_cons;
+                        if (ref) ref_k = key > ref_k ? key : ref_k;
                     }
-                    prefix = next_walk(st);
-                    if (prefix < 0) break;
+                    // queue the records (in pieces that fit the pool) and run the carrier pass over them
+                    const int incl = wave_prefix_sum(nc), ex = incl - nc;
+                    const int total_c = __shfl(incl, 63);
+                    for (int done = 0; done < total_c;) {
+                        const bool mine = nc > 0 && ex >= done && incl <= done + kHsPool;
+                        const unsigned long long bal = __builtin_amdgcn_ballot_w64(mine);
+                        if (mine) {
+                            const int slot = __popcll(bal & ((1ull << lane) - 1ull));
+                            q_key[wave][slot] = key;
+                            q_off[wave][slot] = ex - done;
+                            q_n[wave][slot] = nc;
+                            for (int c = 0; c < nc; ++c) q_pool[wave][ex - done + c] = em.get(c);
+                        }
+                        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                        __builtin_amdgcn_wave_barrier();
+                        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                        hs_carriers(g, w0, nw, __popcll(bal), q_key[wave], q_off[wave], q_n[wave], q_pool[wave], hs_keys);
+                        done = __shfl(incl, 63 - __clzll(bal));
+                        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                        __builtin_amdgcn_wave_barrier();
+                        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                    }
                 }
-                if (over || !next_start(g, p, i0, ws)) break;
-            }
+            });
             if (over && lane == 0) atomicMax(overflow, 1);
         }
         if (all_k) atomicMax(&all_key, all_k);
@@ -227,9 +201,7 @@ GFM_API int gfm_graph_haplotype_scores(gfm_graph_t g, const gfm_motif_t *motifs,
                                        int32_t *d_overflow, int32_t windows_per_run, int32_t haplotypes_per_block, void *stream)
 {
     if (!g) return gfail(GFM_ERR_INVALID, "graph is NULL");
-    if (!g->dev.alt_bits || g->dev.n_hap <= 0)
-        return gfail(GFM_ERR_INVALID, "gfm_graph_haplotype_scores: the graph carries no haplotypes (no bitsets were given to "
-                                      "gfm_graph_create: an XG without its GBWT, or a VCF without samples)");
+    if (!has_haplotypes(*g)) return fail_no_haplotypes("gfm_graph_haplotype_scores");
     if (!motifs || n_motifs < 1 || n_regions < 0 || (n_regions && (!h_starts || !h_stops)) || !d_keys || !d_overflow)
         return gfail(GFM_ERR_INVALID, "bad argument");
     if (flags & ~(uint32_t)GFM_GRAPH_FORWARD_ONLY) return gfail(GFM_ERR_INVALID, "unknown flag");

@@ -1,7 +1,7 @@
 // gfm_graph_hit_alleles.hpp -- the per-hit allele table: for every hit entry of the last fused scoring call, the set of
 // (graph site, allele) constraints of its walk, how many haplotypes of each caller-given group carry it, and (optionally) the
 // carrier set itself.  (Included at the end of graph_extract.hip: it reads the hit entries of gfm_graph_score[_multi] and the
-// plan's tile table and walks the graph as graph_annotate_kernel and hh_mask_hit (gfm_graph_haplotypes.hpp) do.)
+// plan's tile table and re-derives their walks as graph_annotate_kernel and hh_mask_kernel do: hit_walk.)
 //
 // The outputs are indexed by the ENTRY index i, so that they line up with record i of gfm_graph_annotate.  The constraints
 // are the ones the haplotype counting uses -- plain window: the mixed-radix digits of the walk number, one per substitution
@@ -23,81 +23,21 @@ constexpr int kHaBlocks = 8192;                      // wavefronts of ha_entry_k
 constexpr int kHaCompactThreads = 256;
 constexpr long long kHaMaxBatch = 1ll << 24;         // entries per batch: 96 constraints each stay below 2^31 in the int scan
 
-__device__ __forceinline__ int ha_wave_sum(int v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
-
-// The constraints of one hit entry into keys[0 .. n) as site * 4 + allele, in the order they were met (duplicates
-// included) -> n, or -1 when the walk was not found (cannot happen: the score kernel found it).  The derivation is
-// hh_mask_hit's, which is annotate_hit's; only what is kept differs.  Every lane runs it; the lanes share the stores.
+// The constraints of one hit entry (hit_walk) into keys[0 .. n) as site * 4 + allele, in the order they were met (duplicates
+// included), at most kMaxConstraints of them -> n, or -1 when there is no such walk.  The lanes share the stores.
 __device__ __forceinline__ int ha_constraints(const GraphDev &g, int W, const Tile *__restrict__ tiles, int n_tiles,
                                               const GraphHit &hit, int *keys)
 {
-    const int lane = threadIdx.x & 63;
-    const Tile t = tiles[min(max(hit.tile, 0), n_tiles - 1)];
-    const int k = (int)(hit.q2k >> kHitWinShift) & 0xff;
-    const long long q = (hit.q2k & kHitWalkMask) >> 1;
-    const long long p = t.p0 + k;
-    __shared__ SiteRec a_rec[kWaveSites];
-    __shared__ int a_reach[kWaveSites];
-    const int staged = min(t.i_far - t.i_lo + 1, kWaveSites);
-    for (int s_ = threadIdx.x; s_ < staged; s_ += 64) {
-        const int i = t.i_lo + s_;
-        a_rec[s_] = packed_site(g, i);
-        const long long r = (i <= g.n_sites ? g.max_reach[i] : -1ll) - t.p0;
-        a_reach[s_] = (int)max(-1ll, min(r, 0x7fffffffll));
-    }
-    __syncthreads();
-    const WinInfo wi = classify_window(g, TileSites{g, a_rec, a_reach, t.p0, t.i_lo, staged}, p, W, t.limit, t.i_lo, t.i_hi);
-    if (!wi.listed) {
-        unsigned long long dig[2] = {0ull, 0ull};
-        unsigned long long rest = (unsigned long long)q;
-        for (int s_ = wi.ns - 1; s_ >= 0; --s_) {
-            const int nall = 1 + g.n_alts[wi.i0 + s_];
-            dig[s_ >> 5] |= (unsigned long long)take_digit(rest, nall) << (2 * (s_ & 31));
+    const Tile t = hit_tile(tiles, n_tiles, hit);
+    int n = -1;
+    hit_walk<false>(g, W, t, hit, nullptr, [&](int n_cons, auto at, long long, bool) {
+        n = min(n_cons, kMaxConstraints);
+        for (int kk = threadIdx.x & 63; kk < n; kk += 64) {
+            int site, al;
+            at(kk, site, al);
+            keys[kk] = site * 4 + al;
         }
-        const int n = min(wi.ns, kMaxConstraints);
-        for (int kk = lane; kk < n; kk += 64) keys[kk] = (wi.i0 + kk) * 4 + (int)((dig[kk >> 5] >> (2 * (kk & 31))) & 3ull);
-        return n;
-    }
-    __shared__ SiteRec ann_cache[kSiteCache];
-    if (threadIdx.x < kSiteCache) ann_cache[threadIdx.x] = g.site_rec[wi.i0 + threadIdx.x];
-    __syncthreads();
-    const CachedSites cs{g.site_rec, ann_cache, wi.i0, 1};
-    WalkState st;
-    WalkStart ws;
-    NoVisitor nv;
-    long long rest = q, prod = 0;
-    bool found = false, more = true;
-    while (!found && more) {
-        int prefix = 0;
-        for (;;) {
-            const int rc = simulate<NoVisitor, CachedSites, kFusedMaxWalks>(g, cs, p, W, wi.i0, ws, prefix, st, nv, 0, 0, prod, t.limit);
-            if (rc == WALK_OK) {
-                if (rest < prod) { found = true; break; }
-                rest -= prod;
-            }
-            prefix = next_walk(st);
-            if (prefix < 0) break;
-        }
-        if (!found) more = next_start(g, p, wi.i0, ws);
-    }
-    if (!found) return -1;
-    uint8_t km[2 * GFM_MAX_WIDTH];
-    int src[GFM_MAX_WIDTH];
-    int more_cons[kMaxConstraints - 4];
-    DelEmit em(g, km, km + W, src, W, more_cons);
-    long long again = 0;
-    simulate<DelEmit, CachedSites, kFusedMaxWalks>(g, cs, p, W, wi.i0, ws, st.nd, st, em, rest, prod, again, t.limit);
-    if (!(ws.site >= 0 && st.last == p - 1)) for_covering_deletions(g, p, wi.i0, [&](int dsite) { em.add(dsite, 0); });
-    const int n = min(em.n_cons, kMaxConstraints);
-    for (int kk = lane; kk < n; kk += 64) {
-        const int v = em.get(kk);
-        keys[kk] = (v >> 4) * 4 + (v & 3);
-    }
+    });
     return n;
 }
 
@@ -150,21 +90,17 @@ ha_entry_kernel(GraphDev g, int W, const Tile *__restrict__ tiles, int n_tiles, 
             const int word = w0 + lane;
             unsigned long long acc = 0ull;
             if (word < g.hw && n >= 0) {
-                acc = ~0ull;
-                if (word == g.hw - 1 && (g.n_hap & 63)) acc = (1ull << (g.n_hap & 63)) - 1ull;
-                for (int k = 0; k < n_u && acc; ++k) {
-                    const int key = s_key[k];
-                    acc &= allele_word(g, key >> 2, key & 3, word);
-                }
+                auto at = [&](int k, int &site, int &al) { const int key = s_key[k]; site = key >> 2; al = key & 3; };
+                acc = carrier_word<true>(g, n_u, at, word);
             }
             if (masks && word < g.hw) masks[(size_t)i * g.hw + word] = acc;
             tot += __popcll(acc);
             for (int gi = 0; gi < n_groups; ++gi) {
-                const int v = ha_wave_sum(word < g.hw ? __popcll(acc & group_bits[(size_t)gi * g.hw + word]) : 0);
+                const int v = wave_sum(word < g.hw ? __popcll(acc & group_bits[(size_t)gi * g.hw + word]) : 0);
                 if (lane == gi) mine += v;
             }
         }
-        tot = ha_wave_sum(tot);
+        tot = wave_sum(tot);
         if (total && lane == 0) total[i] = tot;
         if (lane < n_groups) group_counts[(size_t)i * n_groups + lane] = mine;
     }
@@ -196,8 +132,6 @@ __global__ void ha_advance_kernel(long long b0, long long nb, const int *__restr
     off[b0 + nb] = next;
 }
 
-inline size_t ha_align(size_t b) { return (b + 255) & ~(size_t)255; }
-
 }  // namespace
 
 GFM_API int gfm_graph_hit_alleles(gfm_graph_t g, const void *d_hits, const uint64_t *d_hit_count, int64_t hit_capacity,
@@ -205,21 +139,14 @@ GFM_API int gfm_graph_hit_alleles(gfm_graph_t g, const void *d_hits, const uint6
                                   int64_t *d_allele_off, int32_t *d_alleles, int64_t allele_capacity, int32_t *d_group_counts,
                                   int32_t *d_total, uint64_t *d_masks, int64_t scratch_bytes, void *stream)
 {
-    if (!g) return gfail(GFM_ERR_INVALID, "graph is NULL");
+    if (const int rc = check_hit_list(g, "gfm_graph_hit_alleles", d_hits, d_hit_count, hit_capacity)) return rc;
     if (n_groups < 0 || n_groups > 64)
         return gfail(GFM_ERR_INVALID, "gfm_graph_hit_alleles: " + std::to_string(n_groups) + " groups (at most 64 per call)");
-    const bool want_bits = n_groups > 0 || d_total || d_masks;
-    if (want_bits && (!g->dev.alt_bits || g->dev.n_hap <= 0))
-        return gfail(GFM_ERR_INVALID, "gfm_graph_hit_alleles: the graph carries no haplotypes (no bitsets were given to "
-                                      "gfm_graph_create: an XG without its GBWT, or a VCF without samples): it has alleles, "
-                                      "but no groups, totals or carrier masks");
+    if ((n_groups > 0 || d_total || d_masks) && !has_haplotypes(*g))
+        return fail_no_haplotypes("gfm_graph_hit_alleles", ": it has alleles, but no groups, totals or carrier masks");
     FusedPlan *P = g->plan;
-    if (!P) return gfail(GFM_ERR_INVALID, "gfm_graph_hit_alleles: no gfm_graph_score call on this handle");
-    if (hit_capacity < 0 || allele_capacity < 0 || !d_allele_off || (allele_capacity && !d_alleles))
-        return gfail(GFM_ERR_INVALID, "bad argument");
+    if (allele_capacity < 0 || !d_allele_off || (allele_capacity && !d_alleles)) return gfail(GFM_ERR_INVALID, "bad argument");
     if (n_groups > 0 && (!d_group_bits || (hit_capacity && !d_group_counts))) return gfail(GFM_ERR_INVALID, "NULL group buffer");
-    if (hit_capacity > 0 && (!d_hits || !d_hit_count)) return gfail(GFM_ERR_INVALID, "NULL device buffer");
-    if (hit_capacity > 0x7fffffffll) return gfail(GFM_ERR_INVALID, "hit capacity beyond 2^31");
     const hipStream_t st = static_cast<hipStream_t>(stream);
     const int hw = g->dev.hw;
     if (const int rc = g->serialise(st)) return rc;
@@ -237,9 +164,9 @@ GFM_API int gfm_graph_hit_alleles(gfm_graph_t g, const void *d_hits, const uint6
     size_t cub_bytes = 0;
     GX_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, cub_bytes, static_cast<int *>(nullptr), static_cast<int *>(nullptr),
                                             (int)batch, st));
-    const size_t b_cnt = ha_align(sizeof(int) * (size_t)batch);
-    const size_t b_stage = ha_align(sizeof(int) * (size_t)batch * kMaxConstraints);
-    const size_t total_bytes = 256 + 2 * b_cnt + b_stage + ha_align(cub_bytes);
+    const size_t b_cnt = align256(sizeof(int) * (size_t)batch);
+    const size_t b_stage = align256(sizeof(int) * (size_t)batch * kMaxConstraints);
+    const size_t total_bytes = 256 + 2 * b_cnt + b_stage + align256(cub_bytes);
     unsigned char *mem = nullptr;
     GX_TRY(hipMallocAsync(reinterpret_cast<void **>(&mem), total_bytes, st));
     long long *base = reinterpret_cast<long long *>(mem);

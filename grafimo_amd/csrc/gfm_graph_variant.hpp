@@ -43,17 +43,53 @@ template <class F>
 __device__ inline bool present_by_bitsets(const GraphDev &g, int n, F at)
 {
     if (!g.alt_bits || g.n_hap <= 0) return false;
-    for (int word = 0; word < g.hw; ++word) {
-        unsigned long long acc = ~0ull;
-        if (word == g.hw - 1 && (g.n_hap & 63)) acc = (1ull << (g.n_hap & 63)) - 1ull;
-        for (int k = 0; k < n && acc; ++k) {
-            int site, al;
-            at(k, site, al);
-            acc &= allele_word(g, site, al, word);
-        }
-        if (acc) return true;
-    }
+    for (int word = 0; word < g.hw; ++word)
+        if (carrier_word<true>(g, n, at, word)) return true;
     return false;
+}
+
+// Every layout of window p, in the enumeration's order: the starts (plain, then inside the insertions anchored at p - 1),
+// per start the layout odometer; body(ws, st, prod) per layout that exists, prod = its walks.  Uniform over a wavefront
+// whose lanes all call it.  -> true: the window holds more than MAXW walks (or a layout does, or a walk decides too
+// often), the enumeration was left there.
+template <long long MAXW, class B>
+__device__ __forceinline__ bool for_window_layouts(const GraphDev &g, long long p, int W, int i0, long long limit, B body)
+{
+    const GlobalSites sites{g.site_rec};
+    WalkStart ws;
+    long long total = 0;
+    for (;;) {
+        WalkState st;
+        NoVisitor nv;
+        int prefix = 0;
+        for (;;) {
+            long long prod = 0;
+            const int rc = simulate<NoVisitor, GlobalSites, MAXW>(g, sites, p, W, i0, ws, prefix, st, nv, 0, 0, prod, limit);
+            if (rc == WALK_OVERFLOW) return true;
+            if (rc == WALK_OK) {
+                total += prod;
+                if (total > MAXW) return true;
+                body(ws, st, prod);
+            }
+            prefix = next_walk(st);
+            if (prefix < 0) break;
+        }
+        if (!next_start(g, p, i0, ws)) return false;
+    }
+}
+
+// Walk q of the prod walks of layout (ws, st) replayed into `em`: its bases (src[j] >= 0: reference base src[j], to be
+// fetched) and its constraints, those of the deletions that cover the window's first base included (not for a walk that
+// never leaves the insertion it starts in) -> the position behind its last base.
+template <long long MAXW>
+__device__ __forceinline__ long long replay_walk(const GraphDev &g, long long p, int W, int i0, const WalkStart &ws,
+                                                 const WalkState &st, long long q, long long prod, long long limit, DelEmit &em)
+{
+    WalkState s2 = st;
+    long long again = 0;
+    simulate<DelEmit, GlobalSites, MAXW>(g, GlobalSites{g.site_rec}, p, W, i0, ws, st.nd, s2, em, q, prod, again, limit);
+    if (!(ws.site >= 0 && s2.last == p - 1)) for_covering_deletions(g, p, i0, [&](int d) { em.add(d, 0); });
+    return s2.last + 1;
 }
 
 template <bool RESOLVE>
@@ -68,83 +104,61 @@ graph_variant_kernel(GraphDev g, const unsigned *__restrict__ ftab, int W, int m
         const VarWin vw = wins[wi];
         const long long p = vw.p, limit = vw.limit;
         const int i0 = lower_bound_pos(g.pos, g.n_sites, p);
-        const GlobalSites sites{g.site_rec};
-        WalkStart ws;
-        long long total = 0;
-        bool over = false;
-        for (;;) {                                     // the starts: plain, then inside insertions anchored at p - 1
-            WalkState st;
-            NoVisitor nv;
-            int prefix = 0;
-            for (;;) {                                 // the layouts of this start (uniform over the wave)
-                long long prod = 0;
-                const int rc = simulate<NoVisitor, GlobalSites, kVarMaxWalks>(g, sites, p, W, i0, ws, prefix, st, nv, 0, 0, prod, limit);
-                if (rc == WALK_OVERFLOW) { over = true; break; }
-                if (rc == WALK_OK) {
-                    total += prod;
-                    if (total > kVarMaxWalks) { over = true; break; }
-                    for (long long q = lane; q < prod; q += kVarThreads) {
-                        uint8_t km[GFM_MAX_WIDTH], kr[GFM_MAX_WIDTH];
-                        int src[GFM_MAX_WIDTH];
-                        int more[kMaxConstraints - 4];
-                        DelEmit em(g, km, kr, src, W, more);
-                        WalkState s2 = st;
-                        long long again = 0;
-                        simulate<DelEmit, GlobalSites, kVarMaxWalks>(g, sites, p, W, i0, ws, st.nd, s2, em, q, prod, again, limit);
-                        if (!(ws.site >= 0 && s2.last == p - 1)) for_covering_deletions(g, p, i0, [&](int d) { em.add(d, 0); });
-                        if (em.n_cons == 0) continue;  // a walk over no site: no allele's footprint
-                        unsigned sum = 0u;
-                        int bad = 0;
-                        for (int j = 0; j < W; ++j) {
-                            if (src[j] >= 0) {
-                                km[j] = g.ref[src[j]];
-                                kr[W - 1 - j] = complement(km[j]);
+        const bool over = for_window_layouts<kVarMaxWalks>(g, p, W, i0, limit, [&](const WalkStart &ws, const WalkState &st,
+                                                                                   long long prod) {
+            for (long long q = lane; q < prod; q += kVarThreads) {
+                uint8_t km[GFM_MAX_WIDTH], kr[GFM_MAX_WIDTH];
+                int src[GFM_MAX_WIDTH];
+                int more[kMaxConstraints - 4];
+                DelEmit em(g, km, kr, src, W, more);
+                const long long end = replay_walk<kVarMaxWalks>(g, p, W, i0, ws, st, q, prod, limit, em);
+                if (em.n_cons == 0) continue;  // a walk over no site: no allele's footprint
+                unsigned sum = 0u;
+                int bad = 0;
+                for (int j = 0; j < W; ++j) {
+                    if (src[j] >= 0) {
+                        km[j] = g.ref[src[j]];
+                        kr[W - 1 - j] = complement(km[j]);
+                    }
+                    const unsigned c = base_code(km[j]);
+                    sum += ftab[j * 8 + (c & 7u)];
+                    bad |= (int)(c >> 2);
+                }
+                int sc[2];
+                sc[0] = bad ? min_val : (int)(sum & 0xffffu);
+                sc[1] = bad ? min_val : (int)(sum >> 16);
+                auto at = [&](int kk, int &site, int &al) { const int v = em.get(kk); site = v >> 4; al = v & 3; };
+                int present = keep_zero ? 1 : -1;      // -1: not tested yet
+                for (int sd = 0; sd < (forward_only ? 1 : 2); ++sd) {
+                    const long long start = sd ? end : p, stop = sd ? p : end;
+                    for (int k = 0; k < em.n_cons; ++k) {
+                        int site, al;
+                        at(k, site, al);
+                        const size_t slot = (size_t)site * 4 + (size_t)al;
+                        const unsigned long long key = variant_key(sc[sd], start, stop, sd == 0, g.pos[site]);
+                        const unsigned long long cur = __atomic_load_n(&keys[slot], __ATOMIC_RELAXED);
+                        if (RESOLVE ? key != cur : key <= cur) continue;
+                        if (present < 0) present = present_by_bitsets(g, em.n_cons, at) ? 1 : 0;
+                        if (!present) break;
+                        if constexpr (!RESOLVE) {
+                            atomicMax(&keys[slot], key);
+                        } else {
+                            const unsigned long long r = atomicAdd(rec_count, 1ull);
+                            if ((long long)r < rec_cap) {
+                                gfm_variant_rec_t &o = recs[r];
+                                o.slot = (int32_t)slot;
+                                o.score = sc[sd];
+                                o.start = start;
+                                o.stop = stop;
+                                o.strand = sd ? '-' : '+';
+                                for (int j = 0; j < W; ++j) o.kmer[j] = sd ? kr[j] : km[j];
                             }
-                            const unsigned c = base_code(km[j]);
-                            sum += ftab[j * 8 + (c & 7u)];
-                            bad |= (int)(c >> 2);
-                        }
-                        const long long end = s2.last + 1;
-                        int sc[2];
-                        sc[0] = bad ? min_val : (int)(sum & 0xffffu);
-                        sc[1] = bad ? min_val : (int)(sum >> 16);
-                        auto at = [&](int kk, int &site, int &al) { const int v = em.get(kk); site = v >> 4; al = v & 3; };
-                        int present = keep_zero ? 1 : -1;      // -1: not tested yet
-                        for (int sd = 0; sd < (forward_only ? 1 : 2); ++sd) {
-                            const long long start = sd ? end : p, stop = sd ? p : end;
-                            for (int k = 0; k < em.n_cons; ++k) {
-                                int site, al;
-                                at(k, site, al);
-                                const size_t slot = (size_t)site * 4 + (size_t)al;
-                                const unsigned long long key = variant_key(sc[sd], start, stop, sd == 0, g.pos[site]);
-                                const unsigned long long cur = __atomic_load_n(&keys[slot], __ATOMIC_RELAXED);
-                                if (RESOLVE ? key != cur : key <= cur) continue;
-                                if (present < 0) present = present_by_bitsets(g, em.n_cons, at) ? 1 : 0;
-                                if (!present) break;
-                                if constexpr (!RESOLVE) {
-                                    atomicMax(&keys[slot], key);
-                                } else {
-                                    const unsigned long long r = atomicAdd(rec_count, 1ull);
-                                    if ((long long)r < rec_cap) {
-                                        gfm_variant_rec_t &o = recs[r];
-                                        o.slot = (int32_t)slot;
-                                        o.score = sc[sd];
-                                        o.start = start;
-                                        o.stop = stop;
-                                        o.strand = sd ? '-' : '+';
-                                        for (int j = 0; j < W; ++j) o.kmer[j] = sd ? kr[j] : km[j];
-                                    }
-                                }
-                            }
-                            if (present == 0) break;
                         }
                     }
+                    if (present == 0) break;
                 }
-                prefix = next_walk(st);
-                if (prefix < 0) break;
             }
-            if (over || !next_start(g, p, i0, ws)) break;
-        }
+        });
         if (over && lane == 0) atomicMax(overflow, 1);
     }
 }

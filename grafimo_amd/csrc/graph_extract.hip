@@ -164,6 +164,22 @@ __device__ __forceinline__ int wave_prefix_sum(int v)
     v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, false);      // row_bcast:31 into rows 2 and 3
     return v;
 }
+// the sum over the wavefront's 64 lanes, in every lane
+__device__ __forceinline__ int wave_sum(int v)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+    return v;
+}
+__device__ __forceinline__ long long wave_sum_ll(long long v)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const int lo_ = __shfl_xor((int)(v & 0xffffffffll), off), hi_ = __shfl_xor((int)(v >> 32), off);
+        v += ((long long)hi_ << 32) | (unsigned)lo_;
+    }
+    return v;
+}
 
 // A walk may start inside an insertion anchored at p - 1 (start coordinate p): `pre_site` = that site (or -1),
 // `pre_t` = offset of its first base inside the inserted string.  next_start() steps through the starts of
@@ -2504,6 +2520,31 @@ GFM_API int gfm_graph_annotate(gfm_graph_t g, const void *d_hits, const uint64_t
     GX_TRY(hipGetLastError());
     return g->called(static_cast<hipStream_t>(stream));
 }
+
+// ---- what the entry points of the per-haplotype / per-hit tables below share
+namespace {
+
+// the hit list of the handle's last gfm_graph_score[_multi] call as a table's entry point receives it (`fn`: its name)
+int check_hit_list(gfm_graph_t g, const char *fn, const void *d_hits, const uint64_t *d_hit_count, int64_t hit_capacity)
+{
+    if (!g) return gfail(GFM_ERR_INVALID, "graph is NULL");
+    if (!g->plan) return gfail(GFM_ERR_INVALID, std::string(fn) + ": no gfm_graph_score call on this handle");
+    if (hit_capacity < 0) return gfail(GFM_ERR_INVALID, "bad argument");
+    if (hit_capacity > 0 && (!d_hits || !d_hit_count)) return gfail(GFM_ERR_INVALID, "NULL device buffer");
+    if (hit_capacity > 0x7fffffffll) return gfail(GFM_ERR_INVALID, "hit capacity beyond 2^31");
+    return GFM_OK;
+}
+
+bool has_haplotypes(const gfm_graph &g) { return g.dev.alt_bits && g.dev.n_hap > 0; }
+int fail_no_haplotypes(const char *fn, const char *then = "")
+{
+    return gfail(GFM_ERR_INVALID, std::string(fn) + ": the graph carries no haplotypes (no bitsets were given to "
+                                  "gfm_graph_create: an XG without its GBWT, or a VCF without samples)" + then);
+}
+
+inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+}  // namespace
 
 #include "gfm_graph_variant.hpp"
 #include "gfm_graph_haplotypes.hpp"
