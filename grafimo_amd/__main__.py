@@ -184,6 +184,19 @@ def buildvg(argv):
     print("Elapsed time %.2fs" % (time.time() - start))
 
 
+# the per-graph result tables: option -> (its flag, what the rows of -s / of scan_graph's TSV files lack for it)
+_GRAPH_TABLES = {"variant_effects": ("--variant-effects", "alleles"), "haplotype_hits": ("--haplotype-hits", "walks"),
+                 "haplotype_scores": ("--haplotype-scores", "walks"), "hit_alleles": ("--hit-alleles", "walks"),
+                 "hit_pairs": ("--hit-pairs", "walks"), "hit_linkage": ("--hit-linkage", "walks")}
+
+
+def _graph_only(a, table):
+    """refuse a graph table asked for over the rows of -s"""
+    if getattr(a, table) and a.sequences:
+        flag, lacks = _GRAPH_TABLES[table]
+        sys.exit(f"ERROR: {flag} needs the graph (-g / -d with -b, or -l -v -b): the rows of -s carry no {lacks}")
+
+
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
     if argv and argv[0] == "buildvg":                  # the reference's two workflows (__main__.py:119-415); findmotif is the default
@@ -206,33 +219,27 @@ def main(argv=None):
         if len(set(a.chroms_find)) != len(a.chroms_find):
             sys.exit('ERROR: Duplicated chromosome names given to "--chroms-find"')
     from_graph = not from_vg and bool(a.linear_genome or a.vcf or a.bedfile)
-    if a.variant_effects and a.sequences:
-        sys.exit("ERROR: --variant-effects needs the graph (-g / -d with -b, or -l -v -b): the rows of -s carry no alleles")
+    _graph_only(a, "variant_effects")
     if a.variant_effects and a.qval_t:
         sys.exit("ERROR: --variant-effects has no q-values: its rows are kept on p < -t, which --qvalueT makes a q-value "
                  "threshold (drop --qvalueT)")
-    if a.haplotype_hits and a.sequences:
-        sys.exit("ERROR: --haplotype-hits needs the graph (-g / -d with -b, or -l -v -b): the rows of -s carry no walks")
-    if a.haplotype_scores and a.sequences:
-        sys.exit("ERROR: --haplotype-scores needs the graph (-g / -d with -b, or -l -v -b): the rows of -s carry no walks")
+    _graph_only(a, "haplotype_hits")
+    _graph_only(a, "haplotype_scores")
     if a.haplotype_groups and not (a.hit_alleles or a.hit_pairs):
         sys.exit("ERROR: --haplotype-groups goes with --hit-alleles or --hit-pairs")
     if a.pair_gap is not None and not a.hit_pairs:
         sys.exit("ERROR: --pair-gap goes with --hit-pairs")
     if a.pair_gap is not None and a.pair_gap[0] > a.pair_gap[1]:
         sys.exit(f"ERROR: --pair-gap MIN MAX: {a.pair_gap[0]} > {a.pair_gap[1]}")
-    if a.hit_pairs and a.sequences:
-        sys.exit("ERROR: --hit-pairs needs the graph (-g / -d with -b, or -l -v -b): the rows of -s carry no walks")
+    _graph_only(a, "hit_pairs")
     if (a.linkage_flank is not None or a.linkage_r2 is not None) and not a.hit_linkage:
         sys.exit("ERROR: --linkage-flank and --linkage-r2 go with --hit-linkage")
     if a.linkage_flank is not None and a.linkage_flank < 0:
         sys.exit(f"ERROR: --linkage-flank {a.linkage_flank} < 0")
     if a.linkage_r2 is not None and not 0.0 <= a.linkage_r2 <= 1.0:
         sys.exit(f"ERROR: --linkage-r2 {a.linkage_r2} outside [0, 1]")
-    if a.hit_linkage and a.sequences:
-        sys.exit("ERROR: --hit-linkage needs the graph (-g / -d with -b, or -l -v -b): the rows of -s carry no walks")
-    if a.hit_alleles and a.sequences:
-        sys.exit("ERROR: --hit-alleles needs the graph (-g / -d with -b, or -l -v -b): the rows of -s carry no walks")
+    _graph_only(a, "hit_linkage")
+    _graph_only(a, "hit_alleles")
     if not from_vg and (from_graph == bool(a.sequences) or (from_graph and not (a.linear_genome and a.vcf and a.bedfile))):
         sys.exit("ERROR: give -g XG / -d DIR with -b BED, or -s DIR, or all of -l FASTA -v VCF -b BED")
     if a.cores <= 0:
@@ -284,121 +291,71 @@ def main(argv=None):
             print_results(res, a.debug)
         else:
             write_results(res, motif, len(motifs), wf, a.debug)
+
+    def source(table):
+        """-> (graph, regions, the first chromosome's GraphIndex) as the tables' compute_* take them"""
+        if not from_vg:
+            return graphs, region_lists, graphs[0].index
+        from .extract_regions import _manifest_prep, read_manifest
+        manifest = read_manifest(sequences_loc)
+        if manifest is None:
+            sys.exit(f"ERROR: {_GRAPH_TABLES[table][0]} needs the graph; scan_graph left TSV rows, which carry no "
+                     f"{_GRAPH_TABLES[table][1]}")
+        return manifest, None, _manifest_prep(manifest).graphs[0].index
+
+    def groups(first_index):
+        """--haplotype-groups FILE -> {group: [haplotype columns]}, or None"""
+        if not a.haplotype_groups:
+            return None
+        from .graph_tables import haplotype_column_names
+        from .hit_alleles import read_haplotype_groups
+        return read_haplotype_groups(a.haplotype_groups, haplotype_column_names(first_index))
+
+    def emit(tables, write, show, count):
+        """a table per motif: printed with -f like the report (no file written), else written and its size reported"""
+        for motif, t in zip(motifs, tables):
+            if a.text_only:
+                show(t)
+                continue
+            print(f"{count(t)} written to {write(t, motif, len(motifs), wf)}")
+
     if a.variant_effects:
         from .variant_effects import compute_variant_effects_many, write_variant_effects
-        if from_vg:
-            from .extract_regions import read_manifest
-            manifest = read_manifest(sequences_loc)
-            if manifest is None:
-                sys.exit("ERROR: --variant-effects needs the graph; scan_graph left TSV rows, which carry no alleles")
-            effects = compute_variant_effects_many(motifs, manifest, None, a.debug, wf)
-        else:
-            effects = compute_variant_effects_many(motifs, graphs, region_lists, a.debug, wf)
-        for motif, table in zip(motifs, effects):
-            if a.text_only:                            # -f: printed like the report, no file written
-                print(table.to_string(index=False))
-                continue
-            path = write_variant_effects(table, motif, len(motifs), wf)
-            print(f"{len(table)} variant effect rows written to {path}")
+        graph, regions, _ = source("variant_effects")
+        emit(compute_variant_effects_many(motifs, graph, regions, a.debug, wf), write_variant_effects,
+             lambda t: print(t.to_string(index=False)), lambda t: f"{len(t)} variant effect rows")
     if a.haplotype_hits:
         from .haplotype_hits import compute_haplotype_hits_many, print_haplotype_hits, write_haplotype_hits
-        if from_vg:
-            from .extract_regions import read_manifest
-            manifest = read_manifest(sequences_loc)
-            if manifest is None:
-                sys.exit("ERROR: --haplotype-hits needs the graph; scan_graph left TSV rows, which carry no walks")
-            matrices = compute_haplotype_hits_many(motifs, manifest, None, a.debug, wf)
-        else:
-            matrices = compute_haplotype_hits_many(motifs, graphs, region_lists, a.debug, wf)
-        for motif, hh in zip(motifs, matrices):
-            if a.text_only:                            # -f: printed like the report, no file written
-                print_haplotype_hits(hh)
-                continue
-            path = write_haplotype_hits(hh, motif, len(motifs), wf)
-            print(f"{hh.counts.shape[0]} x {hh.counts.shape[1]} haplotype hit counts written to {path}")
+        graph, regions, _ = source("haplotype_hits")
+        emit(compute_haplotype_hits_many(motifs, graph, regions, a.debug, wf), write_haplotype_hits, print_haplotype_hits,
+             lambda hh: f"{hh.counts.shape[0]} x {hh.counts.shape[1]} haplotype hit counts")
     if a.haplotype_scores:
         from .haplotype_scores import compute_haplotype_scores_many, print_haplotype_scores, write_haplotype_scores
-        if from_vg:
-            from .extract_regions import read_manifest
-            manifest = read_manifest(sequences_loc)
-            if manifest is None:
-                sys.exit("ERROR: --haplotype-scores needs the graph; scan_graph left TSV rows, which carry no walks")
-            tables = compute_haplotype_scores_many(motifs, manifest, None, a.debug, wf)
-        else:
-            tables = compute_haplotype_scores_many(motifs, graphs, region_lists, a.debug, wf)
-        for motif, hs in zip(motifs, tables):
-            if a.text_only:                            # -f: printed like the report, no file written
-                print_haplotype_scores(hs)
-                continue
-            path = write_haplotype_scores(hs, motif, len(motifs), wf)
-            print(f"{hs.best.shape[0]} x {hs.best.shape[1]} haplotype best scores written to {path}")
+        graph, regions, _ = source("haplotype_scores")
+        emit(compute_haplotype_scores_many(motifs, graph, regions, a.debug, wf), write_haplotype_scores, print_haplotype_scores,
+             lambda hs: f"{hs.best.shape[0]} x {hs.best.shape[1]} haplotype best scores")
     if a.hit_alleles:
-        from .haplotype_hits import haplotype_column_names
-        from .hit_alleles import compute_hit_alleles_many, print_hit_alleles, read_haplotype_groups, write_hit_alleles
-        if from_vg:
-            from .extract_regions import _manifest_prep, read_manifest
-            manifest = read_manifest(sequences_loc)
-            if manifest is None:
-                sys.exit("ERROR: --hit-alleles needs the graph; scan_graph left TSV rows, which carry no walks")
-            source, source_regions = manifest, None
-            first_index = _manifest_prep(manifest).graphs[0].index
-        else:
-            source, source_regions = graphs, region_lists
-            first_index = graphs[0].index
-        groups = None
-        if a.haplotype_groups:
-            groups = read_haplotype_groups(a.haplotype_groups, haplotype_column_names(first_index))
-        tables = compute_hit_alleles_many(motifs, source, source_regions, a.debug, wf, haplotype_groups=groups)
-        for motif, ha in zip(motifs, tables):
-            if a.text_only:                            # -f: printed like the report, no file written
-                print_hit_alleles(ha)
-                continue
-            path = write_hit_alleles(ha, motif, len(motifs), wf)
-            print(f"{len(ha)} hit allele rows written to {path}")
-    if a.hit_pairs:
-        from .haplotype_hits import haplotype_column_names
-        from .hit_alleles import read_haplotype_groups
+        from .hit_alleles import compute_hit_alleles_many, print_hit_alleles, write_hit_alleles
+        graph, regions, first_index = source("hit_alleles")
+        emit(compute_hit_alleles_many(motifs, graph, regions, a.debug, wf, haplotype_groups=groups(first_index)),
+             write_hit_alleles, print_hit_alleles, lambda ha: f"{len(ha)} hit allele rows")
+    if a.hit_pairs:                                    # (one table per call, not per motif)
         from .hit_pairs import compute_hit_pairs, print_hit_pairs, write_hit_pairs
-        if from_vg:
-            from .extract_regions import _manifest_prep, read_manifest
-            manifest = read_manifest(sequences_loc)
-            if manifest is None:
-                sys.exit("ERROR: --hit-pairs needs the graph; scan_graph left TSV rows, which carry no walks")
-            source, source_regions = manifest, None
-            first_index = _manifest_prep(manifest).graphs[0].index
-        else:
-            source, source_regions = graphs, region_lists
-            first_index = graphs[0].index
-        groups = None
-        if a.haplotype_groups:
-            groups = read_haplotype_groups(a.haplotype_groups, haplotype_column_names(first_index))
+        graph, regions, first_index = source("hit_pairs")
         min_gap, max_gap = a.pair_gap if a.pair_gap is not None else (0, 50)
-        hp = compute_hit_pairs(motifs, source, source_regions, a.debug, wf, haplotype_groups=groups, min_gap=min_gap,
+        hp = compute_hit_pairs(motifs, graph, regions, a.debug, wf, haplotype_groups=groups(first_index), min_gap=min_gap,
                                max_gap=max_gap)
         if a.text_only:                                # -f: printed like the report, no file written
             print_hit_pairs(hp)
         else:
-            path = write_hit_pairs(hp, wf)
-            print(f"{len(hp)} hit pair rows written to {path}")
+            print(f"{len(hp)} hit pair rows written to {write_hit_pairs(hp, wf)}")
     if a.hit_linkage:
         from .hit_linkage import compute_hit_linkage_many, print_hit_linkage, write_hit_linkage
-        if from_vg:
-            from .extract_regions import read_manifest
-            manifest = read_manifest(sequences_loc)
-            if manifest is None:
-                sys.exit("ERROR: --hit-linkage needs the graph; scan_graph left TSV rows, which carry no walks")
-            source, source_regions = manifest, None
-        else:
-            source, source_regions = graphs, region_lists
-        linkage = compute_hit_linkage_many(motifs, source, source_regions, a.debug, wf,
-                                           flank=10000 if a.linkage_flank is None else a.linkage_flank,
-                                           min_r2=0.8 if a.linkage_r2 is None else a.linkage_r2)
-        for motif, hl in zip(motifs, linkage):
-            if a.text_only:                            # -f: printed like the report, no file written
-                print_hit_linkage(hl)
-                continue
-            path = write_hit_linkage(hl, motif, len(motifs), wf)
-            print(f"{len(hl)} hit linkage rows written to {path}")
+        graph, regions, _ = source("hit_linkage")
+        emit(compute_hit_linkage_many(motifs, graph, regions, a.debug, wf,
+                                      flank=10000 if a.linkage_flank is None else a.linkage_flank,
+                                      min_r2=0.8 if a.linkage_r2 is None else a.linkage_r2),
+             write_hit_linkage, print_hit_linkage, lambda hl: f"{len(hl)} hit linkage rows")
     if sequences_loc:
         import shutil
         shutil.rmtree(sequences_loc, ignore_errors=True)

@@ -720,6 +720,17 @@ class DeviceGraph:
             all_ = self._fused_all = torch.empty((n_slots, 16 + 17 * self._fused_cap), dtype=torch.int64, device=self.device)
         return all_[slot], self._fused_cap
 
+    @staticmethod
+    def _entries_ptr(base: int, cap: int) -> int:
+        """the address of a slot's hit entries: behind its 16 control words and `cap` records of 15 words"""
+        return base + 128 + 120 * cap
+
+    def hit_list(self, slot: int = 0):
+        """-> (entries pointer, base pointer -- the control words, [0] the hit count --, capacity) of `slot`'s hit list"""
+        buf, cap = self.fused_buffers(0, slot)
+        base = buf.data_ptr()
+        return self._entries_ptr(base, cap), base, cap
+
     def fused_zero(self, n_slots: int):
         """zero the control words of slots [0, n_slots): one fill"""
         self.fused_buffers(0, n_slots - 1)
@@ -749,7 +760,7 @@ class DeviceGraph:
         handles = (vp * M)(*[d.handle for d in dms])
         cuts = (ctypes.c_int32 * M)(*[int(c) for c in cutoffs])
         hist_p = (vp * M)(*[(h.data_ptr() if h is not None else None) for h in (hists if hists is not None else [None] * M)])
-        hits_p = (vp * M)(*[b_.data_ptr() + 128 + 120 * cap for b_ in bufs])        # (entries: behind the records)
+        hits_p = (vp * M)(*[self._entries_ptr(b_.data_ptr(), cap) for b_ in bufs])
         caps = (ctypes.c_int64 * M)(*([cap] * M))
         cnt_p = (vp * M)(*[b_.data_ptr() for b_ in bufs])
         base0 = bufs[0].data_ptr()
@@ -769,9 +780,8 @@ class DeviceGraph:
     def annotate(self, cutoff=None, qtable=None, stream=None, slot: int = 0):
         """gfm_graph_annotate: the records of the entries the last score() / score_many() left in `slot` (cutoff: device
         int32 [1] or None)."""
-        buf, cap = self.fused_buffers(0, slot)
-        base = buf.data_ptr()
-        nv.check(nv.lib().gfm_graph_annotate(self._h, base + 128 + 120 * cap, base, cap, cutoff.data_ptr() if cutoff is not None else None,
+        entries, base, cap = self.hit_list(slot)
+        nv.check(nv.lib().gfm_graph_annotate(self._h, entries, base, cap, cutoff.data_ptr() if cutoff is not None else None,
                                              qtable.data_ptr() if qtable is not None else None, base + 128,
                                              _stream_ptr(stream)))
 
@@ -1908,6 +1918,15 @@ class _FusedPass:
             raise nv.NativeError(nv.GFM_ERR_OVERFLOW, f"a window of width {self.W} holds more than 2^40 walks through its variant sites, or the "
                                                       f"regions hold more than 2^20 windows of more than 64 walks each (scan fewer regions at a time)")
         self.got = got
+
+    def cutoff(self, m: int):
+        """the device cutoff (int32 [1]) enqueue() gave annotate for motif slot m -- the rows are kept on q with --qvalueT --,
+        else None: what a kernel that reads the hit entries after this pass takes beside them"""
+        return self.dms[m].fused_views(self.dev)[2] if (self.qval_t and self.works is not None) else None
+
+    def n_hits(self, m: int, gi: int) -> int:
+        """the entries motif slot m left on graph handle gi; known since fetch(): no list is longer than its capacity then"""
+        return min(int(self.got[m][gi][0]), self.prep.graphs[gi].fused_buffers(0, m)[1])
 
     def _column_specs(self):
         # the hit rows: filtered (--recomb), in report order (p-value, then the TSV rows' order: entry, window, walk, strand), as

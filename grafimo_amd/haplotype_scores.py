@@ -15,7 +15,6 @@ Rows: the regions of the caller's list in order; columns: <SAMPLE>|1, <SAMPLE>|2
 haplotype_hits).  The hot path is HIP (grafimo_amd/csrc/gfm_graph_hapscores.hpp, gfm_graph_haplotype_scores): the walks are
 enumerated and reduced to one 64-bit key per cell on the device, with no hit list.
 """
-import os
 import sys
 from typing import List, Optional, Sequence, Tuple
 
@@ -23,8 +22,9 @@ import numpy as np
 import pandas as pd
 
 from . import _native as nv
-from .extract_regions import _manifest_prep, _prepare_entries, _stream_ptr, _torch
-from .haplotype_hits import META_COLUMNS, _haplotype_set, _matrix_rows
+from .extract_regions import _stream_ptr, _torch
+from .graph_tables import (META_COLUMNS, _haplotype_set, _matrix_rows, group_by_width, prepare_graphs, require_single_gpu,
+                           scaled_pvalues, scaled_scores, table_path, text_table, write_wide)
 
 COLUMNS_HEAD = META_COLUMNS + ["reference"]
 # the key's fields (gfm_graph_hapscores.hpp): score << 48 | (2^28 - 1 - (left - base)) << 20 | (2^19 - 1 - (right - left)) << 1 | '+'
@@ -77,9 +77,8 @@ class HaplotypeScores:
     def _scores(self):
         if self._score is None:
             full = np.concatenate([self.best, self.reference_best[:, None]], axis=1)
-            some = full >= 0
-            self._score = np.where(some, full.astype(np.float64) / float(self.scale) + float(self.width) * self.offset, np.nan)
-            self._pvalue = np.where(some, np.asarray(self.ptable)[np.where(some, full, 0)], np.nan)
+            self._score = scaled_scores(full, self.scale, self.offset, self.width)
+            self._pvalue = scaled_pvalues(full, self.ptable)
         return self._score, self._pvalue
 
     def _coordinates(self):
@@ -141,15 +140,8 @@ def compute_haplotype_scores_many(motifs: Sequence, graph, regions, debug: bool,
     motifs of one width share one run list and one call.  `windows_per_run` / `haplotypes_per_block` cut the device work
     (0: the library's defaults); the result does not depend on them."""
     from .device import DeviceMotif
-    torch = _torch()
-    dist = torch.distributed
-    if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
-        raise NotImplementedError("the per-haplotype best scores are computed on one GPU: under a process group of more than "
-                                  "one rank, call it outside the group (a gather of the sharded matrices is not built yet)")
-    if graph is None:
-        raise ValueError("no graph: a DeviceGraph / GraphIndex with its regions, lists of both, or a scan_graph manifest "
-                         "(read_manifest gives None when scan_graph left TSV rows: GRAFIMO_SCAN_OUTPUT=manifest asks for one)")
-    prep = _manifest_prep(graph) if isinstance(graph, dict) else _prepare_entries(graph, regions, chrom_names, None, False)
+    require_single_gpu("the per-haplotype best scores", "are", "a gather of the sharded matrices")
+    prep = prepare_graphs(graph, regions, chrom_names)
     H, names = _haplotype_set(prep, haplotype_names, "the per-haplotype best score matrix")
     rows, region_names = _matrix_rows(prep)
     R = len(region_names)
@@ -158,10 +150,7 @@ def compute_haplotype_scores_many(motifs: Sequence, graph, regions, debug: bool,
         base[r] = np.maximum(np.asarray(prep.spans[gi][0], dtype=np.int64), 0)
     forward_only = bool(getattr(args_obj, "noreverse", False))
     out: List[Optional[HaplotypeScores]] = [None] * len(motifs)
-    by_width = {}
-    for i, m in enumerate(motifs):
-        by_width.setdefault(int(m.width), []).append(i)
-    for W, idxs in by_width.items():
+    for W, idxs in group_by_width(motifs).items():
         dms = [DeviceMotif.lease(motifs[i]) for i in idxs]
         try:
             one = len(prep.graphs) == 1 and np.array_equal(rows[0], np.arange(R))
@@ -197,9 +186,6 @@ def compute_haplotype_scores(motif, graph, regions, debug: bool, args_obj, chrom
                                          windows_per_run, haplotypes_per_block)[0]
 
 
-_CELL_BYTES = 1 << 25                                 # bytes of cell text the writer makes at a time
-
-
 def _score_strings(values: np.ndarray) -> List[bytes]:
     """the log-odds scores as DataFrame.to_csv writes a float column (the report's `score`): one string per value"""
     if len(values) == 0:
@@ -208,30 +194,13 @@ def _score_strings(values: np.ndarray) -> List[bytes]:
     return [t.encode() for t in text.split("\n")[:-1]]
 
 
-def _cell_table(hs: HaplotypeScores) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
-    """-> (codes int64 [R, H + 1]: the reference column first, 0 for an empty cell; tab uint8 [V, D]: per code its text and a
-    tab; ln [V]: its length) -- one string per distinct scaled score, selected, no Python step per cell"""
+def _cell_table(hs: HaplotypeScores) -> Tuple[np.ndarray, List[bytes]]:
+    """-> (codes int64 [R, H + 1]: the reference column first, 0 for an empty cell; the text of every code) -- one string
+    per distinct scaled score"""
     full = np.concatenate([hs.reference_best[:, None], hs.best], axis=1).astype(np.int64)
     vals = np.unique(full[full >= 0])
-    strings = [b""] + _score_strings(vals.astype(np.float64) / float(hs.scale) + float(hs.width) * hs.offset)
-    codes = np.where(full >= 0, np.searchsorted(vals, np.maximum(full, 0)) + 1, 0)
-    D = max(len(s) for s in strings) + 1
-    tab = np.zeros((len(strings), D), dtype=np.uint8)
-    ln = np.empty(len(strings), dtype=np.int64)
-    for v, t in enumerate(strings):
-        tab[v, :len(t)] = np.frombuffer(t, dtype=np.uint8)
-        tab[v, len(t)] = ord("\t")
-        ln[v] = len(t) + 1
-    return codes, tab, ln
-
-
-def _rows_text(codes: np.ndarray, tab: np.ndarray, ln: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
-    """codes [n, C] -> (bytes of the n lines' cells, tab-separated, each line ending in '\\n'; byte length per line)"""
-    D = tab.shape[1]
-    cells = tab[codes]                                        # [n, C, D]
-    cells[:, -1, :][np.arange(D)[None, :] == ln[codes[:, -1]][:, None] - 1] = ord("\n")
-    keep = np.arange(D)[None, None, :] < ln[codes][:, :, None]
-    return cells[keep], ln[codes].sum(axis=1)
+    strings = [b""] + _score_strings(scaled_scores(vals, hs.scale, hs.offset, hs.width))
+    return np.where(full >= 0, np.searchsorted(vals, np.maximum(full, 0)) + 1, 0), strings
 
 
 def write_haplotype_scores(hs: HaplotypeScores, motif, motif_num: int, args_obj, out=None) -> Optional[str]:
@@ -239,41 +208,10 @@ def write_haplotype_scores(hs: HaplotypeScores, motif, motif_num: int, args_obj,
     write_results uses for this motif -> the path written.  `out`: a binary stream to write to instead (-f: stdout).
     Columns: motif_id, motif_alt_id, sequence_name, reference, one per haplotype; a cell holds the log-odds score of the
     best row, written as the report writes its score column, and is empty where there is no row."""
-    from .res_writer import DEFAULT_OUTDIR
-    path = None
-    if out is None:
-        outdir = getattr(args_obj, "outdir", DEFAULT_OUTDIR)
-        dirname_default = outdir == DEFAULT_OUTDIR
-        if dirname_default:
-            outdir = "_".join(["grafimo_out", str(os.getpid()), motif.motif_id])
-        os.makedirs(outdir, exist_ok=True)
-        name = "grafimo_haplotype_scores" if (dirname_default or motif_num <= 1) else "_".join(["grafimo_haplotype_scores", motif.motif_id])
-        path = os.path.join(outdir, name + ".tsv")
-        fh = open(path, "wb")
-    else:
-        fh = out
-    try:
-        fh.write(("\t".join(COLUMNS_HEAD + list(hs.haplotype_names)) + "\n").encode())
-        head = f"{hs.motif_id}\t{hs.motif_alt_id}\t"
-        codes, tab, ln = _cell_table(hs)
-        chunk = max(1, _CELL_BYTES // max(1, codes.shape[1] * tab.shape[1]))
-        for r0 in range(0, codes.shape[0], chunk):
-            text, lens = _rows_text(codes[r0:r0 + chunk], tab, ln)
-            ends = np.cumsum(lens)
-            mv = memoryview(text)
-            parts = []
-            at = 0
-            for name, e in zip(hs.region_names[r0:r0 + chunk].tolist(), ends.tolist()):     # a step per ROW
-                parts.append(f"{head}{name}\t".encode())
-                parts.append(mv[at:e])
-                at = e
-            fh.writelines(parts)
-    finally:
-        if out is None:
-            fh.close()
-        else:
-            fh.flush()
-    return path
+    codes, strings = _cell_table(hs)
+    return write_wide(out if out is not None else table_path("grafimo_haplotype_scores", args_obj, motif, motif_num),
+                      COLUMNS_HEAD + list(hs.haplotype_names), f"{hs.motif_id}\t{hs.motif_alt_id}\t", hs.region_names, codes,
+                      *text_table(strings))
 
 
 def print_haplotype_scores(hs: HaplotypeScores) -> None:

@@ -16,7 +16,6 @@ gfm_graph_hit_alleles (HIP, grafimo_amd/csrc/gfm_graph_hit_alleles.hpp) works on
 ENTRY --, and gfm_graph_hit_order (the report's ordering code, csrc/hit_table.cpp) says which entry became which row.
 """
 import ctypes
-import os
 import sys
 import warnings
 from typing import Dict, List, Mapping, Optional, Sequence, Tuple
@@ -25,8 +24,9 @@ import numpy as np
 import pandas as pd
 
 from . import _native as nv
-from .extract_regions import _FusedPass, _manifest_prep, _prepare_entries, _stream_ptr, _torch
-from .haplotype_hits import _haplotype_set, _matrix_rows
+from .extract_regions import _FusedPass, _stream_ptr, _torch
+from .graph_tables import (_haplotype_set, _matrix_rows, _site_columns, group_by_width, prepare_graphs, require_single_gpu,
+                           table_path, write_frame)
 
 MAX_GROUPS = 64
 # room for the constraints of a call's first try, per hit entry (a walk has a handful); tests set it to 0 to take the path
@@ -80,8 +80,7 @@ class HitAlleles:
 
     def _allele_strings(self) -> np.ndarray:
         """one string per entry of the CSR arrays -- POS:REF>ALT for an ALT, POS:REF for a REF allele, as
-        variant_effects._site_columns prints a site --, made once per distinct (entry, site, allele)"""
-        from .variant_effects import _site_columns
+        graph_tables._site_columns prints a site --, made once per distinct (entry, site, allele)"""
         n = len(self.allele)
         out = np.empty(n, dtype=object)
         if not n:
@@ -192,8 +191,7 @@ def _entry_alleles(g, p, m: int, n_hits: int, cut, G: int, d_groups, want_total:
     """gfm_graph_hit_alleles over the entries motif slot m left on graph g -> (off int64 [n + 1], packed int32, group counts
     int32 [n, G], totals int32 [n] or None, masks uint64 [n, hw] or None) on the host"""
     torch = _torch()
-    buf, cap = g.fused_buffers(0, m)
-    base = buf.data_ptr()
+    entries, base, _cap = g.hit_list(m)
     dev = p.dev
     off = torch.empty(n_hits + 1, dtype=torch.int64, device=dev)
     gc = torch.empty((n_hits, G), dtype=torch.int32, device=dev)
@@ -203,7 +201,7 @@ def _entry_alleles(g, p, m: int, n_hits: int, cut, G: int, d_groups, want_total:
     while True:
         packed = torch.empty(max(room, 1), dtype=torch.int32, device=dev)
         nv.check(nv.lib().gfm_graph_hit_alleles(
-            g._h, base + 128 + 120 * cap, base, n_hits, cut.data_ptr() if cut is not None else None, G,
+            g._h, entries, base, n_hits, cut.data_ptr() if cut is not None else None, G,
             d_groups.data_ptr() if G else None, off.data_ptr(), packed.data_ptr() if room else None, room,
             gc.data_ptr() if (G and n_hits) else None, total.data_ptr() if total is not None else None,
             masks.data_ptr() if masks is not None else None, int(scratch_bytes), sp))
@@ -280,14 +278,8 @@ def compute_hit_alleles_many(motifs: Sequence, graph, regions, debug: bool, args
     one width share one enumeration of the walks (as compute_results_from_graph_many).  `scratch_bytes`: the device budget
     of the call's staging (0: the library's default, 256 MB); the result does not depend on it."""
     torch = _torch()
-    dist = torch.distributed
-    if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
-        raise NotImplementedError("the per-hit allele table is computed on one GPU: under a process group of more than one "
-                                  "rank, call it outside the group (a gather of the sharded tables is not built yet)")
-    if graph is None:
-        raise ValueError("no graph: a DeviceGraph / GraphIndex with its regions, lists of both, or a scan_graph manifest "
-                         "(read_manifest gives None when scan_graph left TSV rows: GRAFIMO_SCAN_OUTPUT=manifest asks for one)")
-    prep = _manifest_prep(graph) if isinstance(graph, dict) else _prepare_entries(graph, regions, chrom_names, None, False)
+    require_single_gpu("the per-hit allele table", "is", "a gather of the sharded tables")
+    prep = prepare_graphs(graph, regions, chrom_names)
     with_haps = all(g.index.alt_bits is not None and int(g.index.n_haplotypes) > 0 for g in prep.graphs)
     H, names = 0, []
     if haplotype_groups or carriers:
@@ -310,11 +302,8 @@ def compute_hit_alleles_many(motifs: Sequence, graph, regions, debug: bool, args
             indexes[int(e)] = g.index
     listing_of = _matrix_rows(prep)[0]                  # per graph handle: the caller's region listing of its regions
     out: List[Optional[HitAlleles]] = [None] * len(motifs)
-    by_width = {}
-    for i, m in enumerate(motifs):
-        by_width.setdefault(int(m.width), []).append(i)
     sp = _stream_ptr(None)
-    for W, idxs in by_width.items():
+    for W, idxs in group_by_width(motifs).items():
         p = _FusedPass([motifs[i] for i in idxs], prep, debug, args_obj, None)
         try:
             p.enqueue()
@@ -322,12 +311,10 @@ def compute_hit_alleles_many(motifs: Sequence, graph, regions, debug: bool, args
             d_groups = torch.from_numpy(bits.view(np.int64)).to(p.dev) if G else None
             per_motif = []
             for m in range(len(idxs)):
-                dm = p.dms[m]
-                cut = dm.fused_views(p.dev)[2] if (p.qval_t and p.works is not None) else None     # as _FusedPass.enqueue
+                cut = p.cutoff(m)
                 per_part = []
                 for gi, g in enumerate(prep.graphs):
-                    n_hits = min(int(p.got[m][gi][0]), g.fused_buffers(0, m)[1])      # known since fetch()
-                    per_part.append(_entry_alleles(g, p, m, n_hits, cut, G, d_groups, H > 0, carriers, hw, scratch_bytes, sp))
+                    per_part.append(_entry_alleles(g, p, m, p.n_hits(m, gi), cut, G, d_groups, H > 0, carriers, hw, scratch_bytes, sp))
                 per_motif.append(per_part)
             specs = p._column_specs()
             orders = [_report_order(spec) for spec in specs]
@@ -373,21 +360,7 @@ def compute_hit_alleles(motif, graph, regions, debug: bool, args_obj, chrom_name
 def write_hit_alleles(ha: HitAlleles, motif, motif_num: int, args_obj, out=None) -> Optional[str]:
     """grafimo_hit_alleles.tsv (grafimo_hit_alleles_<motif_id>.tsv for one of several motifs) in the directory
     write_results uses for this motif -> the path written.  `out`: a text stream to write to instead (-f: stdout)."""
-    from .res_writer import DEFAULT_OUTDIR
-    table = ha.to_frame()
-    if out is not None:
-        table.to_csv(out, sep="\t", index=False)
-        out.flush()
-        return None
-    outdir = getattr(args_obj, "outdir", DEFAULT_OUTDIR)
-    dirname_default = outdir == DEFAULT_OUTDIR
-    if dirname_default:
-        outdir = "_".join(["grafimo_out", str(os.getpid()), motif.motif_id])
-    os.makedirs(outdir, exist_ok=True)
-    name = "grafimo_hit_alleles" if (dirname_default or motif_num <= 1) else "_".join(["grafimo_hit_alleles", motif.motif_id])
-    path = os.path.join(outdir, name + ".tsv")
-    table.to_csv(path, sep="\t", index=False, encoding="utf-8")
-    return path
+    return write_frame(ha, out if out is not None else table_path("grafimo_hit_alleles", args_obj, motif, motif_num))
 
 
 def print_hit_alleles(ha: HitAlleles) -> None:

@@ -4,7 +4,7 @@ The per-hit allele table and the pair table look INSIDE the k-mer.  This one ans
 lies near a peak but in no motif -- which predicted binding sites travel with it?  That is linkage disequilibrium between
 a report row's carrier set and the allele bitsets of the sites around it, and only a haplotype-resolved graph has both.
 
-All coordinates are the report's: 0-based reference offsets, as GraphIndex.pos (variant_effects._site_columns prints
+All coordinates are the report's: 0-based reference offsets, as GraphIndex.pos (graph_tables._site_columns prints
 pos + 1).  A report ROW has lo = min(start, stop), hi = max(start, stop) and its carrier set C, n_hit = |C| = its
 haplotype_frequency; H is the number of haplotypes.  An ALLELE is (site s, ALT a) of the row's chromosome entry,
 1 <= a <= n_alts[s], with carrier set A = alt_bits[s, a - 1], n_allele = |A|.  REF alleles are not listed (at a biallelic
@@ -29,7 +29,6 @@ the device's count, i.e. with that slack.  The defaults flank = 10 000 and min_r
 product defaults, not measured quantities.
 """
 import ctypes
-import os
 import sys
 from typing import List, Optional, Sequence
 
@@ -37,8 +36,8 @@ import numpy as np
 import pandas as pd
 
 from . import _native as nv
-from .extract_regions import _manifest_prep, _prepare_entries, _stream_ptr, _torch
-from .haplotype_hits import _haplotype_set
+from .extract_regions import _stream_ptr, _torch
+from .graph_tables import _haplotype_set, _site_columns, prepare_graphs, require_single_gpu, table_path, write_frame
 from .hit_alleles import HitAlleles, compute_hit_alleles_many
 
 ROW_COLUMNS = ["sequence_name", "motif_id", "motif_alt_id", "start", "stop", "strand", "score", "p-value", "matched_sequence",
@@ -247,7 +246,6 @@ class HitLinkage:
 
     def _variant_strings(self) -> np.ndarray:
         """POS:REF>ALT per link, as HitAlleles._allele_strings prints an ALT allele"""
-        from .variant_effects import _site_columns
         out = np.empty(len(self), dtype=object)
         for e in np.unique(self.entry).tolist():
             sel = np.flatnonzero(self.entry == e)
@@ -316,18 +314,12 @@ def compute_hit_linkage_many(motifs: Sequence, graph, regions, debug: bool, args
     A graph without haplotype bitsets, graphs of different haplotype sets, more than 32 768 haplotypes, flank < 0 or min_r2
     outside [0, 1]: ValueError; more than `max_links` cells listed by the device for one motif: OverflowError naming the
     count.  `rows_per_tile`, `slots_per_chunk`, `scratch_bytes` as link_rows takes them: the result does not depend on them."""
-    torch = _torch()
-    dist = torch.distributed
-    if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
-        raise NotImplementedError("the hit-linkage table is computed on one GPU: under a process group of more than one rank, "
-                                  "call it outside the group (a gather of the sharded tables is not built yet)")
+    require_single_gpu("the hit-linkage table", "is", "a gather of the sharded tables")
     if int(flank) < 0:
         raise ValueError(f"flank {flank} < 0")
     if not 0.0 <= float(min_r2) <= 1.0:
         raise ValueError(f"min_r2 {min_r2} outside [0, 1]")
-    if graph is None:
-        raise ValueError("no graph: a DeviceGraph / GraphIndex with its regions, lists of both, or a scan_graph manifest")
-    prep = _manifest_prep(graph) if isinstance(graph, dict) else _prepare_entries(graph, regions, chrom_names, None, False)
+    prep = prepare_graphs(graph, regions, chrom_names)
     H, _names = _haplotype_set(prep, haplotype_names, "the hit-linkage table")      # (the refusals, before any pass runs)
     if H > MAX_HAPLOTYPES:
         raise ValueError(f"{H} haplotypes: the linkage counts are exact in int64 up to {MAX_HAPLOTYPES}")
@@ -348,21 +340,7 @@ def compute_hit_linkage(motif, graph, regions, debug: bool, args_obj, chrom_name
 def write_hit_linkage(hl: HitLinkage, motif, motif_num: int, args_obj, out=None) -> Optional[str]:
     """grafimo_hit_linkage.tsv (grafimo_hit_linkage_<motif_id>.tsv for one of several motifs) in the directory
     write_hit_alleles uses for this motif -> the path written.  `out`: a text stream to write to instead (-f: stdout)."""
-    from .res_writer import DEFAULT_OUTDIR
-    table = hl.to_frame()
-    if out is not None:
-        table.to_csv(out, sep="\t", index=False)
-        out.flush()
-        return None
-    outdir = getattr(args_obj, "outdir", DEFAULT_OUTDIR)
-    dirname_default = outdir == DEFAULT_OUTDIR
-    if dirname_default:
-        outdir = "_".join(["grafimo_out", str(os.getpid()), motif.motif_id])
-    os.makedirs(outdir, exist_ok=True)
-    name = LINKAGE_FILE if (dirname_default or motif_num <= 1) else "_".join([LINKAGE_FILE, motif.motif_id])
-    path = os.path.join(outdir, name + ".tsv")
-    table.to_csv(path, sep="\t", index=False, encoding="utf-8")
-    return path
+    return write_frame(hl, out if out is not None else table_path(LINKAGE_FILE, args_obj, motif, motif_num))
 
 
 def print_hit_linkage(hl: HitLinkage) -> None:

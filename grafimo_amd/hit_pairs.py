@@ -22,7 +22,6 @@ compute_hit_alleles_many(..., carriers=True), so the selection is the report's o
 non-overlapping sites at most 50 reference bases apart -- is a product default, not a measured quantity.
 """
 import ctypes
-import os
 import sys
 from typing import List, Mapping, Optional, Sequence
 
@@ -30,13 +29,13 @@ import numpy as np
 import pandas as pd
 
 from . import _native as nv
-from .extract_regions import _manifest_prep, _prepare_entries, _stream_ptr, _torch
-from .haplotype_hits import _haplotype_set, _matrix_rows
+from .extract_regions import _stream_ptr, _torch
+from .graph_tables import _haplotype_set, _matrix_rows, prepare_graphs, require_single_gpu, table_path, write_frame
 from .hit_alleles import MAX_GROUPS, HitAlleles, compute_hit_alleles_many
 
 SIDE_COLUMNS = ["motif_id", "motif_alt_id", "start", "stop", "strand", "score", "p-value", "matched_sequence",
                 "haplotype_frequency"]
-PAIRS_FILE = "grafimo_hit_pairs.tsv"
+PAIRS_FILE = "grafimo_hit_pairs"
 _COORD_LIMIT = 1 << 61
 
 
@@ -194,16 +193,10 @@ def compute_hit_pairs(motifs: Sequence, graph, regions, debug: bool, args_obj, c
     """The hit-pair table of the motif set (see the module's docstring).  `graph` / `regions`, args_obj, `chrom_names`,
     `haplotype_names` and `haplotype_groups` as compute_hit_alleles_many takes them.  A graph without haplotype bitsets or
     graphs of different haplotype sets: ValueError; more than `max_pairs` pairs: OverflowError naming the count."""
-    torch = _torch()
-    dist = torch.distributed
-    if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
-        raise NotImplementedError("the hit-pair table is computed on one GPU: under a process group of more than one rank, "
-                                  "call it outside the group (a gather of the sharded tables is not built yet)")
+    require_single_gpu("the hit-pair table", "is", "a gather of the sharded tables")
     if int(min_gap) > int(max_gap):
         raise ValueError(f"min_gap {min_gap} > max_gap {max_gap}")
-    if graph is None:
-        raise ValueError("no graph: a DeviceGraph / GraphIndex with its regions, lists of both, or a scan_graph manifest")
-    prep = _manifest_prep(graph) if isinstance(graph, dict) else _prepare_entries(graph, regions, chrom_names, None, False)
+    prep = prepare_graphs(graph, regions, chrom_names)
     _haplotype_set(prep, haplotype_names, "the hit-pair table")         # (the refusals, before any pass runs)
     region_names = _matrix_rows(prep)[1]
     tables = compute_hit_alleles_many(motifs, graph, regions, debug, args_obj, chrom_names, haplotype_names, haplotype_groups,
@@ -241,19 +234,7 @@ def compute_hit_pairs(motifs: Sequence, graph, regions, debug: bool, args_obj, c
 def write_hit_pairs(hp: HitPairs, args_obj, out=None) -> Optional[str]:
     """grafimo_hit_pairs.tsv, one file per call: in the -o directory, or with the default output directory in
     grafimo_out_<pid>_pairs -> the path written.  `out`: a text stream to write to instead (-f: stdout)."""
-    from .res_writer import DEFAULT_OUTDIR
-    table = hp.to_frame()
-    if out is not None:
-        table.to_csv(out, sep="\t", index=False)
-        out.flush()
-        return None
-    outdir = getattr(args_obj, "outdir", DEFAULT_OUTDIR)
-    if outdir == DEFAULT_OUTDIR:
-        outdir = "_".join(["grafimo_out", str(os.getpid()), "pairs"])
-    os.makedirs(outdir, exist_ok=True)
-    path = os.path.join(outdir, PAIRS_FILE)
-    table.to_csv(path, sep="\t", index=False, encoding="utf-8")
-    return path
+    return write_frame(hp, out if out is not None else table_path(PAIRS_FILE, args_obj, tag="pairs"))
 
 
 def print_hit_pairs(hp: HitPairs) -> None:

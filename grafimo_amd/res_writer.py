@@ -23,6 +23,17 @@ from .utils import PHASE, SOURCE, TP, exception_handler
 DEFAULT_OUTDIR = "default_out_dir_name"   # utils.py:28
 
 
+def output_dir(args_obj, tag: str):
+    """-> (the directory the results go to, made here; whether it is the default one): args_obj.outdir when the user named
+    one, else grafimo_out_<PID>_<tag> -- the motif's id, for the files of one motif"""
+    outdir = getattr(args_obj, "outdir", DEFAULT_OUTDIR)
+    dirname_default = outdir == DEFAULT_OUTDIR
+    if dirname_default:
+        outdir = "_".join(["grafimo_out", str(os.getpid()), tag])
+    os.makedirs(outdir, exist_ok=True)
+    return outdir, dirname_default
+
+
 def _columns(data: pd.DataFrame, no_qvalue: bool, debug: bool):
     """The column lists writeGFF3 walks (utils.dftolist, utils.py:496-560)."""
     if not isinstance(data, pd.DataFrame):
@@ -87,16 +98,12 @@ def write_results(results: pd.DataFrame, motif: Motif, motif_num: int, args_obj,
         exception_handler(TypeError, f"Expected int, got {type(motif_num).__name__}.\n", debug)
     if motif_num <= 0:
         exception_handler(ValueError, "No motif searched. Probably something went wrong.\n", debug)
-    outdir = getattr(args_obj, "outdir", DEFAULT_OUTDIR)
     no_qvalue = bool(args_obj.noqvalue)
     verbose = bool(getattr(args_obj, "verbose", False))
     if int(getattr(args_obj, "top_graphs", 0) or 0) > 0:
         exception_handler(NotImplementedError,
                           "--top-graphs needs the external vg and dot binaries (out of scope).\n", debug)
-    dirname_default = outdir == DEFAULT_OUTDIR
-    if dirname_default:
-        outdir = "_".join(["grafimo_out", str(os.getpid()), motif.motif_id])
-    os.makedirs(outdir, exist_ok=True)
+    outdir, dirname_default = output_dir(args_obj, motif.motif_id)
     print(f"\nWriting results in {outdir}.\n")
     prefix = "grafimo_out"
     if not dirname_default and motif_num > 1:

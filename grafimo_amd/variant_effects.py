@@ -35,7 +35,8 @@ import numpy as np
 import pandas as pd
 
 from . import _native as nv
-from .extract_regions import GraphIndex, _prepare_entries, _stream_ptr, _torch, cached_device_graph
+from .extract_regions import GraphIndex, _stream_ptr, _torch
+from .graph_tables import _site_columns, group_by_width, prepare_graphs, require_single_gpu, table_path, write_frame
 
 VARIANT_REC_DTYPE = np.dtype([("slot", "<i4"), ("score", "<i4"), ("start", "<i8"), ("stop", "<i8"), ("strand", "u1"),
                               ("pad", "u1", (7,)), ("kmer", "u1", (nv.GFM_MAX_WIDTH,))])
@@ -53,57 +54,15 @@ _FIRST_REC_CAPACITY = 0
 def _entries(graph, regions, chrom_names):
     """-> [(DeviceGraph, starts, stops, name)] in the caller's entry order, one per distinct graph handle (entries that
     share a handle are scanned as one list of regions, named after the first of them)."""
-    if graph is None:
-        raise ValueError("no graph: a DeviceGraph / GraphIndex with its regions, lists of both, or a scan_graph manifest "
-                         "(read_manifest gives None when scan_graph left TSV rows: GRAFIMO_SCAN_OUTPUT=manifest asks for one)")
-    if isinstance(graph, dict):                       # a scan_graph manifest
-        graph, regions, chrom_names = ([cached_device_graph(e["index"]) for e in graph["entries"]],
-                                       [e["regions"] for e in graph["entries"]], [e["chrom"] for e in graph["entries"]])
-    many = isinstance(graph, (list, tuple))
-    ents = list(graph) if many else [graph]
-    names = ([chrom_names] if isinstance(chrom_names, str) else list(chrom_names)) if chrom_names is not None \
-        else [(g_.chrom if isinstance(g_, GraphIndex) else g_.index.chrom) for g_ in ents]
-    prep = _prepare_entries(graph, regions, chrom_names, None, False)
+    prep = prepare_graphs(graph, regions, chrom_names)
+    runs, base = prep.labels.runs, prep.labels.base             # (one run of regions per entry, with the entry's name)
     out = []
     for gi, g_ in enumerate(prep.graphs):
-        first = int(prep.entry_of[gi][0]) if len(prep.entry_of[gi]) else gi
         s_, e_ = prep.spans[gi]
+        run = int(np.searchsorted(base, prep.region_base[gi], side="right")) - 1      # the entry of the handle's first region
         out.append((g_, np.ascontiguousarray(s_, dtype=np.int64), np.ascontiguousarray(e_, dtype=np.int64),
-                    names[min(first, len(names) - 1)]))
+                    runs[min(run, len(runs) - 1)][0]))
     return out
-
-
-def _site_columns(index: GraphIndex, site: np.ndarray, alt: np.ndarray):
-    """for the rows (site, alt): position (1-based), REF and ALT strings, ref_haplotypes, alt_haplotypes -- made for the
-    table's rows only (a chromosome holds millions of sites and thousands of haplotypes)"""
-    ref = np.asarray(index.ref)
-    pos = np.asarray(index.pos, dtype=np.int64)[site]
-    n = len(site)
-    H = int(index.n_haplotypes) if index.alt_bits is not None else 0
-    alt_h = np.zeros(n, dtype=np.int64)
-    ref_h = np.full(n, H, dtype=np.int64)
-    if H and n:
-        bits = np.asarray(index.alt_bits, dtype=np.uint64)[site]                        # [n, 3, hw]
-        na = np.asarray(index.n_alts, dtype=np.int64)[site]
-        used = (np.arange(3)[None, :] < na[:, None])[..., None]
-        bits = np.where(used, bits, np.uint64(0))
-        pc = lambda w: np.unpackbits(w.view(np.uint8), axis=-1, bitorder="little")[..., :H].sum(axis=-1)    # noqa: E731
-        alt_h = pc(np.ascontiguousarray(bits[np.arange(n), alt - 1])).astype(np.int64)
-        ref_h = H - pc(np.ascontiguousarray(np.bitwise_or.reduce(bits, axis=1))).astype(np.int64)
-    refs, alts = [], []
-    for i, a, p in zip(site.tolist(), alt.tolist(), pos.tolist()):
-        anchor = chr(int(ref[p]))
-        if index.del_len[i] > 0:
-            refs.append(bytes(ref[p:p + 1 + int(index.del_len[i])]).decode())
-            alts.append(anchor)
-        elif index.ins_len[i] > 0:
-            o = int(index.ins_off[i])
-            refs.append(anchor)
-            alts.append(anchor + bytes(index.ins_bases[o:o + int(index.ins_len[i])]).decode())
-        else:
-            refs.append(anchor)
-            alts.append(chr(int(index.alt_bases[i, a - 1])))
-    return pos + 1, np.array(refs, dtype=object), np.array(alts, dtype=object), ref_h, alt_h
 
 
 def effect_columns(ptable: np.ndarray, scale: int, offset: float, W: int, n_alts: np.ndarray, recs: np.ndarray,
@@ -196,19 +155,12 @@ def compute_variant_effects_many(motifs: Sequence, graph, regions, debug: bool, 
     """compute_variant_effects for every motif of a set -> one table per motif, in the order of `motifs`.  The motifs of one
     width share the window list of a call; the tables equal the single calls'."""
     from .device import DeviceMotif
-    torch = _torch()
-    dist = torch.distributed
-    if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
-        raise NotImplementedError("the variant effect table is computed on one GPU: under a process group of more than one "
-                                  "rank, call it outside the group (a MAX all-reduce of the key arrays is not built yet)")
+    require_single_gpu("the variant effect table", "is", "a MAX all-reduce of the key arrays")
     threshold = float(args_obj.threshold)
     forward_only, recomb = bool(args_obj.noreverse), bool(args_obj.recomb)
     entries = _entries(graph, regions, chrom_names)
     parts: List[List[pd.DataFrame]] = [[] for _ in motifs]
-    by_width = {}
-    for k, m in enumerate(motifs):
-        by_width.setdefault(int(m.width), []).append(k)
-    for W, ks in by_width.items():
+    for W, ks in group_by_width(motifs).items():
         dms = [DeviceMotif.lease(motifs[k]) for k in ks]
         try:
             for dg, starts, stops, name in entries:
@@ -238,14 +190,4 @@ def compute_variant_effects(motif, graph, regions, debug: bool, args_obj, chrom_
 def write_variant_effects(table: pd.DataFrame, motif, motif_num: int, args_obj) -> str:
     """grafimo_variant_effects.tsv (grafimo_variant_effects_<motif_id>.tsv for one of several motifs) in the directory
     write_results uses for this motif -> the path written."""
-    import os
-    from .res_writer import DEFAULT_OUTDIR
-    outdir = getattr(args_obj, "outdir", DEFAULT_OUTDIR)
-    dirname_default = outdir == DEFAULT_OUTDIR
-    if dirname_default:
-        outdir = "_".join(["grafimo_out", str(os.getpid()), motif.motif_id])
-    os.makedirs(outdir, exist_ok=True)
-    name = "grafimo_variant_effects" if (dirname_default or motif_num <= 1) else "_".join(["grafimo_variant_effects", motif.motif_id])
-    path = os.path.join(outdir, name + ".tsv")
-    table.to_csv(path, sep="\t", index=False, encoding="utf-8")
-    return path
+    return write_frame(table, table_path("grafimo_variant_effects", args_obj, motif, motif_num))

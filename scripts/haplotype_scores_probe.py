@@ -94,7 +94,7 @@ def main():
         best = torch.empty((R, H), dtype=torch.int32, device=dg.device)
         torch.cuda.synchronize()
         ev0.record()
-        nv.check(nv.lib().gfm_graph_haplotype_hits(dg._h, buf.data_ptr() + 128 + 120 * cap, buf.data_ptr(), n_hits, None, R,
+        nv.check(nv.lib().gfm_graph_haplotype_hits(dg._h, *dg.hit_list(0)[:2], n_hits, None, R,
                                                    counts.data_ptr(), best.data_ptr(), 0, _stream_ptr(None)))
         ev1.record()
         torch.cuda.synchronize()

@@ -79,7 +79,7 @@ def main():
             tot = torch.empty(n_hits, dtype=torch.int32, device=dg.device)
             torch.cuda.synchronize()
             ev0.record()
-            nv.check(nv.lib().gfm_graph_hit_alleles(dg._h, buf.data_ptr() + 128 + 120 * cap, buf.data_ptr(), n_hits, None, 5,
+            nv.check(nv.lib().gfm_graph_hit_alleles(dg._h, *dg.hit_list(0)[:2], n_hits, None, 5,
                                                     d_bits.data_ptr(), off.data_ptr(), packed.data_ptr(), 8 * n_hits, gc.data_ptr(),
                                                     tot.data_ptr(), None, 0, _stream_ptr(None)))
             ev1.record()

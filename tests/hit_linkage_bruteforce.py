@@ -103,7 +103,7 @@ def synthetic_input(seed, H, n_rows=300, n_sites=400, span=3000, near=60):
 def check_linkage(hl, entries, flank, min_r2):
     """`hl`: a HitLinkage; `entries`: per chromosome entry its GraphIndex (None for an entry without regions) -> the number
     of links.  Everything exact but the comparison with np.corrcoef (1e-12: it checks the formula, not the table)."""
-    from grafimo_amd.variant_effects import _site_columns
+    from grafimo_amd.graph_tables import _site_columns
     t = hl.table
     rep = t.report
     H = len(t.haplotype_names)

@@ -13,7 +13,7 @@ import pytest
 from grafimo_amd import _native as nv
 from grafimo_amd import extract_regions as xr
 from grafimo_amd import hit_alleles as hal
-from grafimo_amd.variant_effects import _site_columns
+from grafimo_amd.graph_tables import _site_columns
 from test_hit_table_host import _records, _reference_columns
 
 
