@@ -17,6 +17,26 @@ from .device import DeviceMotif, _torch
 HIT_SCORE_BITS = 20  # GFM_HIT_SCORE_BITS: hit entry = (row << 20) | scaled score
 
 
+def score_ring_step(turn: int, n_slots: int, n_arrays: int, tail_reads):
+    """The waiting rule of a score ring shorter than the slot ring, as a pure function (no torch, no GPU).
+    Turn t takes slot t % n_slots and writes score array t % n_arrays, so an array's writers are n_arrays turns apart and
+    the array written at turn t stays untouched for n_arrays - 1 further turns, whatever n_slots is.
+    `tail_reads(w)`: whether the tail of the earlier turn w reads its scores (only asked for turn - n_slots < w < turn).
+    Returns (array, wait): `wait` is the earlier turn that must be through its tail before this turn's score kernel may
+    start, BEYOND the slot-reuse wait for turn - n_slots, or None.  The `done` events are recorded in turn order on one
+    stream, so a wait for turn w covers every turn before w: the youngest earlier writer of the array whose tail reads
+    the scores is the only one to name, and none is named when the slot-reuse wait already covers it or when no writer's
+    tail reads the scores (a p-value scan without regions is paced by its slots alone)."""
+    array = turn % n_arrays
+    oldest = max(0, turn - n_slots + 1)         # everything before it: covered by the slot-reuse wait
+    w = turn - n_arrays
+    while w >= oldest:
+        if tail_reads(w):
+            return array, w
+        w -= n_arrays
+    return array, None
+
+
 class ScanSlot:
     """One set of device buffers for a batch of up to n_rows k-mers."""
 
@@ -37,6 +57,7 @@ class ScanSlot:
         self.done = torch.cuda.Event()
         self.tail_done = torch.cuda.Event()
         self.used = False
+        self.reads_scores = False   # whether the tail of the slot's current batch reads its scores (KmerScanner.enqueue)
         self.gathered = None
         # raw addresses for the ctypes fast path
         self.p_scores = self.scores.data_ptr()
@@ -95,14 +116,17 @@ class KmerScanner:
         if self.collective and side_stream:
             self._gather_stream = torch.cuda.Stream(device=self.device, priority=-1)
         cap = int(hit_capacity) if hit_capacity is not None else int(n_rows)
-        # `score_buffers` < n_slots: the int32 [n_rows] score arrays form a shorter ring than the slots (slot k writes array
-        # k % score_buffers): a batch's `slot.scores` then stays valid for score_buffers - 1 further enqueues only, while its
+        # `score_buffers` < n_slots: the int32 [n_rows] score arrays form a shorter ring than the slots.  The array belongs to the
+        # TURN, not to the slot (turn t writes array t % score_buffers; enqueue() points slot.scores at it): a batch's
+        # `slot.scores` then stays valid for score_buffers - 1 further enqueues only, for every pair of ring lengths, while its
         # histogram, q-table and hit list stay valid for n_slots - 1.  What it is for: a fourth slot gives the host a third step of
         # slack against a tail that runs long, but a fourth 80 MB score array pushes the write-through stores' working set
         # (3 x 80 MB fits the 256 MB Infinity Cache, 4 x 80 MB does not: the score kernel 83 -> 87 us, profiles/r06_step_gap.txt).
         nb = n_slots if score_buffers is None else max(1, min(int(score_buffers), n_slots))
         ring = [torch.empty(int(n_rows), dtype=torch.int32, device=self.device) for _ in range(nb)]
         self.slots = [ScanSlot(dm, n_rows, cap, self.device, scores=ring[k % nb]) for k in range(n_slots)]
+        self._ring = ring
+        self._ring_p = [a.data_ptr() for a in ring]
         self._score_ring = nb
         # high priority: tail kernels are tiny and sit on the critical path of slot reuse
         self.side = torch.cuda.Stream(device=self.device, priority=-1) if side_stream else None
@@ -185,7 +209,8 @@ class KmerScanner:
         torch = _torch()
         lib = self._lib
         dm = self.dm
-        slot = self.slots[self._turn % len(self.slots)]
+        turn, n_slots = self._turn, len(self.slots)
+        slot = self.slots[turn % n_slots]
         self._turn += 1
         main = torch.cuda.current_stream(self.device)
         main_p = main.cuda_stream
@@ -197,12 +222,20 @@ class KmerScanner:
             else:
                 main.wait_event(slot.done)
         slot.used = True
-        if self._score_ring < len(self.slots) and (on_qvalue or self._regions is not None):
-            # a shorter score ring, and this batch's tail READS the scores (selection on q, per-region best hit): the batch that
-            # wrote this score array last must be through its tail before the score kernel overwrites it
-            prev = self.slots[(self._turn - 1 - self._score_ring) % len(self.slots)]
-            if prev.used and self._turn > self._score_ring:
-                prev.done.synchronize()
+        if self._score_ring < n_slots:
+            # a shorter score ring: this turn's array was written by younger batches than the slot's previous one.  The hazard is
+            # an EARLIER writer's tail still reading the array (per-region best hit, selection on q: gfm_select_hits always,
+            # gfm_select_hits_from when its candidate list overflowed) while this turn's score kernel overwrites it -- whatever
+            # this turn's own tail does.  score_ring_step names the one batch to wait for, if any; its slot has not been
+            # reused yet (it is younger than turn - n_slots), so the slot's `done` event is still that batch's.
+            a, wait = score_ring_step(turn, n_slots, self._score_ring, self._turn_reads_scores)
+            if wait is not None:
+                if self.host_paced:
+                    self.slots[wait % n_slots].done.synchronize()
+                else:
+                    main.wait_event(self.slots[wait % n_slots].done)
+            slot.scores, slot.p_scores = self._ring[a], self._ring_p[a]
+            slot.reads_scores = on_qvalue or self._regions is not None
         # no zeroing on the critical path: the q-value kernel hands the histogram back cleared
         # (GFM_FLAG_CLEAR_HIST) and the hit list restarts through GFM_FLAG_RESET_HITS
         n = int(d_kmers.shape[0])
@@ -277,6 +310,9 @@ class KmerScanner:
             lib.gfm_profile_mark_tail(h, tail_p)
         slot.done.record(tail)
         return slot
+
+    def _turn_reads_scores(self, turn: int) -> bool:
+        return self.slots[turn % len(self.slots)].reads_scores
 
     def _gather(self, slot: ScanSlot):
         """hit buffers ([count | entries], fixed size) of all ranks -> rank 0.  gather moves
