@@ -107,6 +107,12 @@ def get_parser():
     p.add_argument("--haplotype-scores", action="store_true", dest="haplotype_scores",
                    help="also write grafimo_haplotype_scores[_MOTIF].tsv (printed with -f): per region, each haplotype's best "
                         "motif score whatever the threshold, beside the reference's (graph routes only)")
+    p.add_argument("--haplotype-affinity", action="store_true", dest="haplotype_affinity",
+                   help="also write grafimo_haplotype_affinity[_MOTIF].tsv (printed with -f): per region, the log2 of each "
+                        "haplotype's total binding affinity -- the sum of 2^(log-odds / T) over every k-mer of its own "
+                        "sequence --, beside the reference's (graph routes only)")
+    p.add_argument("--affinity-temperature", dest="affinity_temperature", type=float, default=None, metavar="T",
+                   help="with --haplotype-affinity: the temperature T > 0 the log-odds scores are divided by; default 1")
     p.add_argument("--hit-alleles", action="store_true", dest="hit_alleles",
                    help="also write grafimo_hit_alleles[_MOTIF].tsv (printed with -f): the report's rows, each with the variant "
                         "alleles that make its k-mer and, with --haplotype-groups, its carriers per group (graph routes only)")
@@ -186,7 +192,8 @@ def buildvg(argv):
 
 # the per-graph result tables: option -> (its flag, what the rows of -s / of scan_graph's TSV files lack for it)
 _GRAPH_TABLES = {"variant_effects": ("--variant-effects", "alleles"), "haplotype_hits": ("--haplotype-hits", "walks"),
-                 "haplotype_scores": ("--haplotype-scores", "walks"), "hit_alleles": ("--hit-alleles", "walks"),
+                 "haplotype_scores": ("--haplotype-scores", "walks"), "haplotype_affinity": ("--haplotype-affinity", "walks"),
+                 "hit_alleles": ("--hit-alleles", "walks"),
                  "hit_pairs": ("--hit-pairs", "walks"), "hit_linkage": ("--hit-linkage", "walks")}
 
 
@@ -225,6 +232,11 @@ def main(argv=None):
                  "threshold (drop --qvalueT)")
     _graph_only(a, "haplotype_hits")
     _graph_only(a, "haplotype_scores")
+    if a.affinity_temperature is not None and not a.haplotype_affinity:
+        sys.exit("ERROR: --affinity-temperature goes with --haplotype-affinity")
+    if a.affinity_temperature is not None and not a.affinity_temperature > 0:
+        sys.exit(f"ERROR: --affinity-temperature {a.affinity_temperature} is not > 0")
+    _graph_only(a, "haplotype_affinity")
     if a.haplotype_groups and not (a.hit_alleles or a.hit_pairs):
         sys.exit("ERROR: --haplotype-groups goes with --hit-alleles or --hit-pairs")
     if a.pair_gap is not None and not a.hit_pairs:
@@ -334,6 +346,13 @@ def main(argv=None):
         graph, regions, _ = source("haplotype_scores")
         emit(compute_haplotype_scores_many(motifs, graph, regions, a.debug, wf), write_haplotype_scores, print_haplotype_scores,
              lambda hs: f"{hs.best.shape[0]} x {hs.best.shape[1]} haplotype best scores")
+    if a.haplotype_affinity:
+        from .haplotype_affinity import compute_haplotype_affinity_many, print_haplotype_affinity, write_haplotype_affinity
+        graph, regions, _ = source("haplotype_affinity")
+        emit(compute_haplotype_affinity_many(motifs, graph, regions, a.debug, wf,
+                                             temperature=1.0 if a.affinity_temperature is None else a.affinity_temperature),
+             write_haplotype_affinity, print_haplotype_affinity,
+             lambda ha: f"{ha.sums.shape[0]} x {ha.sums.shape[1]} haplotype affinities")
     if a.hit_alleles:
         from .hit_alleles import compute_hit_alleles_many, print_hit_alleles, write_hit_alleles
         graph, regions, first_index = source("hit_alleles")

@@ -196,6 +196,52 @@ graph_hapscore_kernel(GraphDev g, const unsigned *__restrict__ ftab, int W, int 
 
 }  // namespace
 
+// The runs of a call: every region's window starts [s, e - tail] cut into pieces of windows_per_run (0: kHsDefaultRun),
+// staged in the variant table's window buffer of the handle (both are lists of the handle's last call) and uploaded on
+// `st` -> *n_runs; the list is at g->v_wins.
+static int hs_stage_runs(gfm_graph *g, int32_t n_regions, const int64_t *h_starts, const int64_t *h_stops, int W,
+                         int32_t windows_per_run, hipStream_t st, long long *n_runs)
+{
+    const long long ref_len = g->dev.ref_len;
+    const long long per_run = windows_per_run > 0 ? windows_per_run : kHsDefaultRun;
+    const long long tail = g->dev.n_ins > 0 ? 1 : W;
+    constexpr size_t kWords = sizeof(HsRun) / sizeof(long long);
+    if (g->call_pending) GX_TRY(hipEventSynchronize(g->ev_call));      // the last call's upload may still read h_vwins
+    g->h_vwins.clear();
+    for (int r = 0; r < n_regions; ++r) {
+        const long long s = std::max<long long>(h_starts[r], 0), e = std::min<long long>(h_stops[r], ref_len);
+        const long long last = e - tail;
+        if (last < s) continue;
+        const long long pieces = (last - s + per_run) / per_run;
+        for (long long p0 = s; p0 <= last; p0 += per_run) {
+            const HsRun run{p0, std::min(p0 + per_run, last + 1), e, s, r, pieces == 1 ? 1 : 0, 0};
+            const long long *w = reinterpret_cast<const long long *>(&run);
+            g->h_vwins.insert(g->h_vwins.end(), w, w + kWords);
+        }
+    }
+    *n_runs = (long long)(g->h_vwins.size() / kWords);
+    if (*n_runs > 0) {
+        const size_t n_vw = (size_t)*n_runs * (sizeof(HsRun) / sizeof(VarWin));
+        if (n_vw > g->v_cap) {
+            if (g->v_wins) GX_TRY(hipFree(g->v_wins));
+            g->v_wins = nullptr;
+            g->v_cap = 0;
+            GX_TRY(hipMalloc(&g->v_wins, sizeof(VarWin) * n_vw));
+            g->v_cap = n_vw;
+        }
+        GX_TRY(hipMemcpyAsync(g->v_wins, g->h_vwins.data(), sizeof(HsRun) * (size_t)*n_runs, hipMemcpyHostToDevice, st));
+    }
+    return GFM_OK;
+}
+
+// haplotypes of one block: the caller's, or (0) as few blocks as the LDS allows, split evenly
+static int hs_block_haplotypes(int H, int haplotypes_per_block)
+{
+    if (haplotypes_per_block) return haplotypes_per_block;
+    const int blocks = (H + kHsMaxBlockHaps - 1) / kHsMaxBlockHaps;
+    return ((H + blocks - 1) / blocks + 63) / 64 * 64;
+}
+
 GFM_API int gfm_graph_haplotype_scores(gfm_graph_t g, const gfm_motif_t *motifs, int32_t n_motifs, int32_t n_regions,
                                        const int64_t *h_starts, const int64_t *h_stops, uint32_t flags, uint64_t *const *d_keys,
                                        int32_t *d_overflow, int32_t windows_per_run, int32_t haplotypes_per_block, void *stream)
@@ -242,41 +288,10 @@ GFM_API int gfm_graph_haplotype_scores(gfm_graph_t g, const gfm_motif_t *motifs,
     }
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (const int rc = g->serialise(st)) return rc;
-    // ---- the runs: every region's window starts [s, e - tail] cut into pieces of windows_per_run (staged in the variant
-    // table's window buffer of the handle: both are lists of the handle's last call)
-    const long long per_run = windows_per_run > 0 ? windows_per_run : kHsDefaultRun;
-    const long long tail = g->dev.n_ins > 0 ? 1 : W;
-    constexpr size_t kWords = sizeof(HsRun) / sizeof(long long);
-    if (g->call_pending) GX_TRY(hipEventSynchronize(g->ev_call));      // the last call's upload may still read h_vwins
-    g->h_vwins.clear();
-    for (int r = 0; r < n_regions; ++r) {
-        const long long s = std::max<long long>(h_starts[r], 0), e = std::min<long long>(h_stops[r], ref_len);
-        const long long last = e - tail;
-        if (last < s) continue;
-        const long long pieces = (last - s + per_run) / per_run;
-        for (long long p0 = s; p0 <= last; p0 += per_run) {
-            const HsRun run{p0, std::min(p0 + per_run, last + 1), e, s, r, pieces == 1 ? 1 : 0, 0};
-            const long long *w = reinterpret_cast<const long long *>(&run);
-            g->h_vwins.insert(g->h_vwins.end(), w, w + kWords);
-        }
-    }
-    const long long n_runs = (long long)(g->h_vwins.size() / kWords);
+    long long n_runs = 0;
+    if (const int rc = hs_stage_runs(g, n_regions, h_starts, h_stops, W, windows_per_run, st, &n_runs)) return rc;
     if (n_runs > 0) {
-        const size_t n_vw = (size_t)n_runs * (sizeof(HsRun) / sizeof(VarWin));
-        if (n_vw > g->v_cap) {
-            if (g->v_wins) GX_TRY(hipFree(g->v_wins));
-            g->v_wins = nullptr;
-            g->v_cap = 0;
-            GX_TRY(hipMalloc(&g->v_wins, sizeof(VarWin) * n_vw));
-            g->v_cap = n_vw;
-        }
-        GX_TRY(hipMemcpyAsync(g->v_wins, g->h_vwins.data(), sizeof(HsRun) * (size_t)n_runs, hipMemcpyHostToDevice, st));
-        const int H = g->dev.n_hap;
-        int hb = haplotypes_per_block;
-        if (hb == 0) {                                 // as few blocks as the LDS allows, split evenly
-            const int blocks = (H + kHsMaxBlockHaps - 1) / kHsMaxBlockHaps;
-            hb = ((H + blocks - 1) / blocks + 63) / 64 * 64;
-        }
+        const int H = g->dev.n_hap, hb = hs_block_haplotypes(H, haplotypes_per_block);
         const dim3 grid((unsigned)std::min<long long>(n_runs, 1 << 16), (unsigned)((H + hb - 1) / hb));
         const int fwd = (flags & GFM_GRAPH_FORWARD_ONLY) ? 1 : 0;
         const HsRun *runs = static_cast<const HsRun *>(g->v_wins);

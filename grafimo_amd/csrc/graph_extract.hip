@@ -2549,4 +2549,5 @@ inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 #include "gfm_graph_variant.hpp"
 #include "gfm_graph_haplotypes.hpp"
 #include "gfm_graph_hapscores.hpp"
+#include "gfm_graph_hapaffinity.hpp"
 #include "gfm_graph_hit_alleles.hpp"

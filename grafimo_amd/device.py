@@ -60,6 +60,7 @@ class DeviceMotif:
         if sm.ndim != 2 or sm.shape[0] != 4:
             raise ValueError("score_matrix must be [4, W]")
         bg = np.ascontiguousarray(bg, dtype=np.float64)
+        self.score_matrix = sm
         self.width = int(sm.shape[1])
         self.L = RANGE * self.width + 1
         self.min_val = int(min_val)

@@ -667,6 +667,25 @@ int gfm_graph_haplotype_scores(gfm_graph_t g, const gfm_motif_t *motifs, int32_t
                                const int64_t *h_starts, const int64_t *h_stops, uint32_t flags, uint64_t *const *d_keys,
                                int32_t *d_overflow, int32_t windows_per_run, int32_t haplotypes_per_block, void *stream);
 
+/* ------------------------------------------------------------------ per-haplotype total binding affinity (a sum, exact)
+ * For region r and haplotype h: A(r, h) = the sum of w[score(row)] over the rows of gfm_graph_haplotype_scores' Rows(r, h)
+ * -- every k-mer of h's own sequence under the report's region rule, once per strand (one strand with
+ * GFM_GRAPH_FORWARD_ONLY) -- in uint64, with w = d_weights[m], uint64 [table_len of motif m] on the device, indexed by the
+ * scaled score (a k-mer holding N scores the motif's min_val).  The table is taken as given, zeros allowed.  Per motif m,
+ * d_sums[m] uint64 [n_regions][n_hap + 1], zeroed by the caller, receives the sums; column n_hap is the reference path.
+ * Integer adds: the result is exact and depends neither on windows_per_run / haplotypes_per_block (as for
+ * gfm_graph_haplotype_scores) nor on the order of the device's atomics.  max_weight: the largest entry of the tables.  A
+ * cell holds at most rows_bound(r) = 2 * (the bases of region r clipped to the chromosome + ALL inserted bases of the graph)
+ * rows -- a row per strand and base of the haplotype's sequence that starts in the region --, and a region with
+ * rows_bound(r) * max_weight > 2^64 - 1 is refused with GFM_ERR_INVALID before anything is launched.  *d_overflow (zeroed by
+ * the caller) = 1 if a window holds more than 2^24 walks: the sums are not complete.  GFM_ERR_INVALID also when the graph
+ * carries no haplotypes.  Motifs of ONE width.  Enqueue only (host work: the run list; the handle's calls are serialised
+ * as gfm_graph_score's are). */
+int gfm_graph_haplotype_affinity(gfm_graph_t g, const gfm_motif_t *motifs, int32_t n_motifs,
+                                 const uint64_t *const *d_weights, uint64_t max_weight, int32_t n_regions,
+                                 const int64_t *h_starts, const int64_t *h_stops, uint32_t flags, uint64_t *const *d_sums,
+                                 int32_t *d_overflow, int32_t windows_per_run, int32_t haplotypes_per_block, void *stream);
+
 /* ------------------------------------------------------------------ hit pairs: rows close to each other that share carriers
  * Graph-independent (csrc/hit_pairs.hip).  n rows (n < 2^31 - 1) in device memory, in ascending (d_group, d_lo) order:
  * d_group int32, d_lo <= d_hi int64 (|x| < 2^61), d_masks uint64 [n][hw] (hw >= 1 words of a bitset whose unused tail
