@@ -41,6 +41,17 @@ typedef __attribute__((address_space(3))) const u32x2_t lds_cu32x2;
 typedef __attribute__((address_space(3))) const u32x4_t lds_cu32x4;
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 
+// One count into an LDS histogram window, bin `bin` of the window at LDS offset `window`.  The pointer is an
+// address_space(3) one on purpose: where the in-window bin, the N bin and the global spill counter were three
+// atomicAdd() on generic pointers, the compiler merged the destinations into ONE generic pointer and the hot loop
+// booked every row with a FLAT atomic (64-bit address built per row, vector-memory path, counted in vmcnt AND
+// lgkmcnt).  An LDS pointer can only become ds_add_u32.
+__device__ inline void lds_hist_add(unsigned window, unsigned bin)
+{
+    typedef __attribute__((address_space(3))) unsigned lds_u32;
+    __hip_atomic_fetch_add((lds_u32 *)(uintptr_t)(window + 4u * bin), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+
 // STORE = false: the instantiation for callers that pass d_scores == NULL (the product's scans: histogram and hits only).  A
 // per-launch branch instead cost the storing launch 1.5 % (84.6 against 83.3 us for 2e7 rows, same box, scripts/lab_bench.sh).
 template <int W, int MM, bool STORE = true>
@@ -65,11 +76,13 @@ score_quad_kernel(const uint8_t *__restrict__ kmers, long long n, long long row_
     unsigned char *tab = smem;
     unsigned char *stage_base = smem + kTabBytes;
     unsigned *hist[MM];
+    unsigned hist_off[MM];      // the windows' absolute LDS offsets: what the adds of book() address
     {
         unsigned *h = reinterpret_cast<unsigned *>(stage_base + n_waves * SSTRIDE);
 #pragma unroll
         for (int m = 0; m < MM; ++m) {
             hist[m] = h;
+            hist_off[m] = lds_offset(h);
             if (a.m[m].use_hist) h += a.m[m].nb + 1;
         }
     }
@@ -128,10 +141,9 @@ score_quad_kernel(const uint8_t *__restrict__ kmers, long long n, long long row_
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     const unsigned off = (unsigned)(p_score[m][j] - ma.lo);
-                    if (off < (unsigned)ma.nb)
-                        atomicAdd(&hist[m][off], 1u);
-                    else if (p_score[m][j] == ma.min_val)   // a row holding N scores min_val, below every reachable
-                        atomicAdd(&hist[m][ma.nb], 1u);     // sum unless the window holds min_val itself
+                    // a row holding N scores min_val, below every reachable sum unless the window holds min_val itself
+                    if (off < (unsigned)ma.nb || p_score[m][j] == ma.min_val)
+                        lds_hist_add(hist_off[m], min(off, (unsigned)ma.nb));
                     else
                         atomicAdd(&ma.spill[(size_t)(blockIdx.x & (kSpillCopies - 1)) * (size_t)ma.spill_n + (size_t)(p_score[m][j] - ma.spill_lo)], 1u);   // outside the window: rare
                 }
@@ -340,10 +352,8 @@ score_quad_kernel(const uint8_t *__restrict__ kmers, long long n, long long row_
                     if (!no_store) ma.scores[first + k] = sc;
                     if (ma.use_hist) {
                         const unsigned off = (unsigned)(sc - ma.lo);
-                        if (off < (unsigned)ma.nb)
-                            atomicAdd(&hist[m][off], 1u);
-                        else if (sc == ma.min_val)
-                            atomicAdd(&hist[m][ma.nb], 1u);
+                        if (off < (unsigned)ma.nb || sc == ma.min_val)
+                            lds_hist_add(hist_off[m], min(off, (unsigned)ma.nb));
                         else
                             atomicAdd(&ma.spill[(size_t)(blockIdx.x & (kSpillCopies - 1)) * (size_t)ma.spill_n + (size_t)(sc - ma.spill_lo)], 1u);
                     }

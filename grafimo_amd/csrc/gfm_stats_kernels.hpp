@@ -145,6 +145,7 @@ ptable_kernel(const DpJob *__restrict__ jobs)
 // registers needs an EMPTY CU, and next to the persistent score grid it found none -- on the
 // tail stream it simply waited for the score kernel to end (measured: 19 us alone, 76-95 us
 // "overlapped", gating the pipeline).  Small blocks slot in beside resident score workgroups.
+// (Windows of at most kQ1Bins bins take q_table_kernel below, one launch; these three serve the wider ones.)
 //   q_count_kernel : per-block bin totals
 //   q_raw_kernel   : C(s) by block-suffix + in-block scan, raw(s) -> qtable (temporary), block minima
 //   q_final_kernel : prefix minimum -> q(s), cutoff, clears
@@ -350,6 +351,144 @@ __global__ void __launch_bounds__(kQThreads) q_final_kernel(const QJobs jobs)
     if ((int)blockIdx.x >= q.nblk) return;
     q_final_body(q.hist, q.ptable, q.L, q.lo, q.hi, q.min_val, jobs.threshold, jobs.on_qvalue, q.ws, q.qtable,
                  q.cutoff, q.nrows, q.clear, q.nblk);
+}
+
+// ---------------------------------------------------------------------------------------
+// q_table_kernel: the three passes above in ONE launch for windows of at most kQ1Bins bins (blockIdx.x = motif, one
+// workgroup per motif).  In stream order each of the three latency-bound launches costs its dispatch gap whatever it
+// computes, and the resident pipeline's tail (post, q_count, q_raw, q_final) is nearly as long as a step: two launches
+// less shorten the chain and what trails the last score kernel of a burst or of a single scan.
+// Thread t owns the kQ1K consecutive bins lo + t kQ1K ..: their counts, then their raw values, in registers.
+//   C(s)  = the thread's own top-down running sum + the exclusive block suffix sum of the thread totals (integers)
+//   raw   = ptable[s] / ((double)C(s) / n)                    -- the very operations of q_raw_body
+//   q(s)  = min(own bottom-up running minimum, exclusive block prefix minimum of the thread minima, N rows' raw, 1)
+// The sums are integer and fmin of non-NaN values is exact in any association, so every output is bit for bit what the
+// three kernels write.  The workgroup reads all of its input before it writes any output and no other workgroup touches
+// its motif: no scratch (QWork), no raw values parked in the q-table, no barrier beyond __syncthreads().
+// Where it runs: 512 threads = 8 waves = 2 per SIMD at 136 VGPRs (read from the assembly; with the tail-table reads
+// hoisted the compiler keeps counts, probabilities and raw values live side by side) and 152 bytes of LDS.  On its own
+// CU a 16-wave score workgroup holds 4 of the 8 wave slots of each SIMD and at least 4 x 72 = 288 of its 512 VGPRs:
+// 224 are left, room for ONE such wave per SIMD, not two -- so this workgroup does not share a CU with a score
+// workgroup.  It runs on one of the CUs the persistent score grid leaves free (kReserveCUs = 4 always; 23 of 256 at
+// 2e7 rows of W = 19, where the grid is 233 workgroups), any of which holds it whole.  Capping it at 96 VGPRs
+// (amdgpu_waves_per_eu) spilled 160 bytes per lane to scratch and was dropped.
+constexpr int kQ1Threads = 512;
+constexpr int kQ1K = 16;
+constexpr int kQ1Bins = kQ1Threads * kQ1K;     // 8192 >= the 7 425 bins of CTCF; wider windows keep the three kernels
+constexpr int kQ1Waves = kQ1Threads / kWave;
+
+__global__ void __launch_bounds__(kQ1Threads) q_table_kernel(const QJobs jobs)
+{
+    const QJob &q = jobs.j[blockIdx.x];
+    const unsigned long long *hist = q.hist;
+    const double *__restrict__ ptable = q.ptable;
+    double *qtable = q.qtable;
+    unsigned long long *clear = q.clear;
+    const int L = q.L, lo = q.lo, hi = q.hi, min_val = q.min_val;
+    __shared__ unsigned long long sh_cnt[kQ1Waves];
+    __shared__ double sh_min[kQ1Waves];
+    __shared__ unsigned long long sh_n_rows_N;
+    __shared__ int first_s;
+    const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid >> 6;
+    const int j0 = lo + tid * kQ1K;
+    const bool n_outside = min_val < lo || min_val > hi;
+    if (tid == 0) {
+        sh_n_rows_N = n_outside ? hist[min_val] : 0ull;
+        first_s = L;
+    }
+    // counts -> C(s) inside the thread (top-down running sum); `occ` remembers which bins hold rows
+    // Every global read of the kernel goes out here, back to back: beside the score grid a round trip to memory takes
+    // microseconds, and a tail-table read issued only where a bin turns out occupied made sixteen of them in a row
+    // (27-71 us per launch, measured; the three kernels took 18).
+    unsigned long long c[kQ1K];
+    double p[kQ1K];
+    unsigned occ = 0;
+#pragma unroll
+    for (int k = 0; k < kQ1K; ++k) c[k] = j0 + k <= hi ? hist[j0 + k] : 0ull;
+#pragma unroll
+    for (int k = 0; k < kQ1K; ++k) p[k] = j0 + k <= hi ? ptable[j0 + k] : 0.0;
+    const double p_min_val = ptable[min_val];
+    unsigned long long run = 0;
+#pragma unroll
+    for (int k = kQ1K - 1; k >= 0; --k) {
+        occ |= (c[k] != 0ull ? 1u : 0u) << k;
+        run += c[k];
+        c[k] = run;
+    }
+    // exclusive suffix sum of the thread totals over the block
+    unsigned long long cs = run;
+#pragma unroll
+    for (int d = 1; d < kWave; d <<= 1) {
+        const unsigned long long v = __shfl_down(cs, d);
+        if (lane + d < kWave) cs += v;
+    }
+    if (lane == 0) sh_cnt[wave] = cs;
+    __syncthreads();
+    unsigned long long above = cs - run, total = 0;
+#pragma unroll
+    for (int w = 0; w < kQ1Waves; ++w) {
+        const unsigned long long v = sh_cnt[w];
+        total += v;
+        if (w > wave) above += v;
+    }
+    const unsigned long long n_rows_N = sh_n_rows_N;
+    const unsigned long long n = total + n_rows_N;
+    const double nd = (double)n;
+    // raw(s), then the thread's bottom-up running minimum of it
+    double r[kQ1K];
+    double m = INFINITY;
+    unsigned p_below = 0;       // bins whose tail probability is below the threshold
+#pragma unroll
+    for (int k = 0; k < kQ1K; ++k) {
+        double raw = INFINITY;
+        if ((occ >> k) & 1u) raw = p[k] / ((double)(c[k] + above) / nd);
+        p_below |= (p[k] < jobs.threshold ? 1u : 0u) << k;      // (p is not kept: registers)
+        m = fmin(m, raw);
+        r[k] = m;
+    }
+    // exclusive prefix minimum of the thread minima over the block
+    double ms = m;
+#pragma unroll
+    for (int d = 1; d < kWave; d <<= 1) {
+        const double v = __shfl_up(ms, d);
+        if (lane >= d) ms = fmin(ms, v);
+    }
+    if (lane == kWave - 1) sh_min[wave] = ms;
+    double below = __shfl_up(ms, 1);
+    if (lane == 0) below = INFINITY;
+    __syncthreads();
+    double all = INFINITY;
+#pragma unroll
+    for (int w = 0; w < kQ1Waves; ++w) {
+        const double v = sh_min[w];
+        all = fmin(all, v);
+        if (w < wave) below = fmin(below, v);
+    }
+    // rows holding an N sit below every other score: rank n, p = p_table[min_val] (= 1)
+    const double base = n_rows_N ? p_min_val / (nd / nd) : INFINITY;
+    below = fmin(below, base);
+    int first = L;
+#pragma unroll
+    for (int k = kQ1K - 1; k >= 0; --k) {
+        const int j = j0 + k;
+        if (j <= hi) {
+            const double qv = fmin(fmin(r[k], below), 1.0);
+            qtable[j] = qv;
+            if (jobs.on_qvalue ? qv < jobs.threshold : ((p_below >> k) & 1u) != 0) first = j;
+            if (clear) clear[j] = 0ull;
+        }
+    }
+    if (first < L) atomicMin(&first_s, first);
+    // outside the window: 1 below it (p = 1 there), the last running minimum above it
+    const double q_above = fmin(fmin(base, all), 1.0);
+    for (int jj = tid; jj < lo; jj += kQ1Threads) qtable[jj] = fmin(base, 1.0);
+    for (int jj = hi + 1 + tid; jj < L; jj += kQ1Threads) qtable[jj] = q_above;
+    __syncthreads();
+    if (tid == 0) {
+        if (q.cutoff) *q.cutoff = first_s;
+        if (q.nrows) *q.nrows = n;
+        if (clear && n_outside) clear[min_val] = 0ull;
+    }
 }
 
 }  // namespace

@@ -1248,18 +1248,23 @@ GFM_API int gfm_profile_read(gfm_motif_t m, float *h_ms, int capacity, int *n_ou
 }
 
 namespace {
-// q-tables of `count` motifs (<= kQJobs): three launches, blockIdx.y = motif
+// q-tables of `count` motifs (<= kQJobs).  A lone motif whose window has at most kQ1Bins bins: one launch of
+// q_table_kernel; wider ones and groups: the three passes, blockIdx.y = motif.  (q_table_kernel takes up to kQJobs
+// motifs, blockIdx.x = motif, but groups stay on the three passes: where the q-tables of a motif set run in stream
+// order -- fifty motifs, eight a launch -- the one kernel's 26 us against the three's 19 and the fourth launch of a
+// group that straddles kQ1Bins made the step 0.8-1.7 % longer.)
 int launch_qtables(const gfm_motif_t *motifs, int count, uint64_t *const *d_hist, double threshold, int on_qvalue,
                    double *const *d_qtable, int32_t *const *d_cutoff, uint64_t *const *d_nrows, uint32_t flags,
                    hipStream_t st)
 {
-    QJobs jobs{};
-    jobs.threshold = threshold;
-    jobs.on_qvalue = on_qvalue;
-    int max_blk = 0;
+    QJobs one{}, three{};
+    one.threshold = three.threshold = threshold;
+    one.on_qvalue = three.on_qvalue = on_qvalue;
+    int n_one = 0, n_three = 0, max_blk = 0;
     for (int k = 0; k < count; ++k) {
         gfm_motif *m = motifs[k];
-        QJob &q = jobs.j[k];
+        const bool narrow = count == 1 && m->nb <= kQ1Bins;
+        QJob &q = narrow ? one.j[n_one++] : three.j[n_three++];
         q.hist = reinterpret_cast<const unsigned long long *>(d_hist[k]);
         q.ptable = m->d_ptable;
         int qs = 0;                 // this stream's scratch set on this handle
@@ -1283,12 +1288,15 @@ int launch_qtables(const gfm_motif_t *motifs, int count, uint64_t *const *d_hist
         q.clear = (flags & GFM_FLAG_CLEAR_HIST) ? reinterpret_cast<unsigned long long *>(d_hist[k]) : nullptr;
         q.L = m->L; q.lo = m->lo; q.hi = m->hi; q.min_val = m->min_val;
         q.nblk = (m->nb + kQThreads - 1) / kQThreads;   // <= 251 for W <= 64
-        max_blk = std::max(max_blk, q.nblk);
+        if (!narrow) max_blk = std::max(max_blk, q.nblk);
     }
-    const dim3 grid((unsigned)max_blk, (unsigned)count);
-    hipLaunchKernelGGL(q_count_kernel, grid, dim3(kQThreads), 0, st, jobs);
-    hipLaunchKernelGGL(q_raw_kernel, grid, dim3(kQThreads), 0, st, jobs);
-    hipLaunchKernelGGL(q_final_kernel, grid, dim3(kQThreads), 0, st, jobs);
+    if (n_one) hipLaunchKernelGGL(q_table_kernel, dim3((unsigned)n_one), dim3(kQ1Threads), 0, st, one);
+    if (n_three) {
+        const dim3 grid((unsigned)max_blk, (unsigned)n_three);
+        hipLaunchKernelGGL(q_count_kernel, grid, dim3(kQThreads), 0, st, three);
+        hipLaunchKernelGGL(q_raw_kernel, grid, dim3(kQThreads), 0, st, three);
+        hipLaunchKernelGGL(q_final_kernel, grid, dim3(kQThreads), 0, st, three);
+    }
     HIP_TRY(hipGetLastError());
     return GFM_OK;
 }

@@ -25,7 +25,8 @@ for gm in 0:1 1:1 2:1 3:1 0:2 1:2 0:3 1:3; do
 done
 wait
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o "$root/lab/libgfm_$tag.so" "$root/lab/gfm_$tag.o" \
-    "$root/lab"/gfm_${tag}_g?_m?.o "$gx" "$obj/stream_calib.o" "$obj/region_reduce.o" "$obj/tsv_ingest.o" "$obj/vcf_ingest.o" \
-    "$obj/scan_stream.o" "$obj/gfm_workers.o" "$obj/graph_tsv_writer.o" "$obj/hit_table.o" -lpthread -lz
+    "$root/lab"/gfm_${tag}_g?_m?.o "$gx" "$obj/stream_calib.o" "$obj/region_reduce.o" "$obj/hit_pairs.o" "$obj/hit_linkage.o" \
+    "$obj/tsv_ingest.o" "$obj/vcf_ingest.o" "$obj/scan_stream.o" "$obj/gfm_workers.o" "$obj/graph_tsv_writer.o" "$obj/hit_table.o" \
+    "$obj/variant_table.o" -lpthread -lz
 rm -f "$root/lab/gfm_$tag.o" "$root/lab"/gfm_${tag}_g?_m?.o "$root/lab/gfm_${tag}_graph.o"
 echo "built lab/libgfm_$tag.so"
