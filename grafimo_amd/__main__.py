@@ -112,7 +112,14 @@ def get_parser():
                         "haplotype's total binding affinity -- the sum of 2^(log-odds / T) over every k-mer of its own "
                         "sequence --, beside the reference's (graph routes only)")
     p.add_argument("--affinity-temperature", dest="affinity_temperature", type=float, default=None, metavar="T",
-                   help="with --haplotype-affinity: the temperature T > 0 the log-odds scores are divided by; default 1")
+                   help="with --haplotype-affinity or --variant-affinity: the temperature T > 0 the log-odds scores are "
+                        "divided by; default 1")
+    p.add_argument("--variant-affinity", action="store_true", dest="variant_affinity",
+                   help="also write grafimo_variant_affinity[_MOTIF].tsv (printed with -f): per variant, the log2 of the mean "
+                        "total binding affinity of the REF carriers over the allele's footprint beside the ALT carriers', "
+                        "and their difference -- every k-mer counts, whatever the threshold (graph routes only)")
+    p.add_argument("--variant-affinity-delta", dest="variant_affinity_delta", type=float, default=None, metavar="X",
+                   help="with --variant-affinity: keep only the rows with |delta_log2_affinity| >= X; default: every row")
     p.add_argument("--hit-alleles", action="store_true", dest="hit_alleles",
                    help="also write grafimo_hit_alleles[_MOTIF].tsv (printed with -f): the report's rows, each with the variant "
                         "alleles that make its k-mer and, with --haplotype-groups, its carriers per group (graph routes only)")
@@ -193,7 +200,7 @@ def buildvg(argv):
 # the per-graph result tables: option -> (its flag, what the rows of -s / of scan_graph's TSV files lack for it)
 _GRAPH_TABLES = {"variant_effects": ("--variant-effects", "alleles"), "haplotype_hits": ("--haplotype-hits", "walks"),
                  "haplotype_scores": ("--haplotype-scores", "walks"), "haplotype_affinity": ("--haplotype-affinity", "walks"),
-                 "hit_alleles": ("--hit-alleles", "walks"),
+                 "variant_affinity": ("--variant-affinity", "walks"), "hit_alleles": ("--hit-alleles", "walks"),
                  "hit_pairs": ("--hit-pairs", "walks"), "hit_linkage": ("--hit-linkage", "walks")}
 
 
@@ -232,11 +239,16 @@ def main(argv=None):
                  "threshold (drop --qvalueT)")
     _graph_only(a, "haplotype_hits")
     _graph_only(a, "haplotype_scores")
-    if a.affinity_temperature is not None and not a.haplotype_affinity:
-        sys.exit("ERROR: --affinity-temperature goes with --haplotype-affinity")
+    if a.affinity_temperature is not None and not (a.haplotype_affinity or a.variant_affinity):
+        sys.exit("ERROR: --affinity-temperature goes with --haplotype-affinity or --variant-affinity")
     if a.affinity_temperature is not None and not a.affinity_temperature > 0:
         sys.exit(f"ERROR: --affinity-temperature {a.affinity_temperature} is not > 0")
     _graph_only(a, "haplotype_affinity")
+    if a.variant_affinity_delta is not None and not a.variant_affinity:
+        sys.exit("ERROR: --variant-affinity-delta goes with --variant-affinity")
+    if a.variant_affinity_delta is not None and not a.variant_affinity_delta >= 0:
+        sys.exit(f"ERROR: --variant-affinity-delta {a.variant_affinity_delta} is not >= 0")
+    _graph_only(a, "variant_affinity")
     if a.haplotype_groups and not (a.hit_alleles or a.hit_pairs):
         sys.exit("ERROR: --haplotype-groups goes with --hit-alleles or --hit-pairs")
     if a.pair_gap is not None and not a.hit_pairs:
@@ -353,6 +365,13 @@ def main(argv=None):
                                              temperature=1.0 if a.affinity_temperature is None else a.affinity_temperature),
              write_haplotype_affinity, print_haplotype_affinity,
              lambda ha: f"{ha.sums.shape[0]} x {ha.sums.shape[1]} haplotype affinities")
+    if a.variant_affinity:
+        from .variant_affinity import compute_variant_affinity_many, print_variant_affinity, write_variant_affinity
+        graph, regions, _ = source("variant_affinity")
+        emit(compute_variant_affinity_many(motifs, graph, regions, a.debug, wf,
+                                           temperature=1.0 if a.affinity_temperature is None else a.affinity_temperature,
+                                           min_abs_delta=a.variant_affinity_delta or 0.0),
+             write_variant_affinity, print_variant_affinity, lambda va: f"{len(va)} variant affinity rows")
     if a.hit_alleles:
         from .hit_alleles import compute_hit_alleles_many, print_hit_alleles, write_hit_alleles
         graph, regions, first_index = source("hit_alleles")

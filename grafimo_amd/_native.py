@@ -145,6 +145,8 @@ PROTOTYPES = {
                                            c_void_p, c_i32, c_i32, c_void_p]),
     "gfm_graph_haplotype_affinity": (c_int, [c_void_p, c_void_p, c_i32, c_void_p, c_u64, c_i32, c_void_p, c_void_p,
                                              ctypes.c_uint32, c_void_p, c_void_p, c_i32, c_i32, c_void_p]),
+    "gfm_graph_variant_affinity": (c_int, [c_void_p, c_void_p, c_i32, c_void_p, c_i32, c_void_p, c_void_p, ctypes.c_uint32,
+                                           c_void_p, c_void_p, P(c_i64), c_i32, c_void_p]),
     "gfm_hit_pairs": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_i32, c_i64, c_i64, c_i32, c_void_p, c_void_p, c_i64,
                               c_void_p, c_void_p, c_void_p, ctypes.c_uint32, P(c_i64), c_void_p]),
     "gfm_hit_linkage": (c_int, [c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_i64, c_i32, c_i32, c_i64,

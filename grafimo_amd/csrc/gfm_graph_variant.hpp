@@ -165,6 +165,59 @@ graph_variant_kernel(GraphDev g, const unsigned *__restrict__ ftab, int W, int m
 
 }  // namespace
 
+// The windows within reach of a site: starts in [pos - W + 1, pos + 1 + del_len] (a walk that starts inside an insertion
+// anchored at p - 1, on bases a deletion anchored before p removes), merged, cut to every region's window range -> *n_win
+// (start, limit) pairs at g->v_wins, uploaded on `st`.  `unique`: a start that several regions hold is listed once, with the
+// largest limit among them (a walk valid under a smaller limit is valid under a larger one: the union of the regions' walks).
+static int variant_stage_windows(gfm_graph_t g, int W, int n_regions, const int64_t *h_starts, const int64_t *h_stops, bool unique,
+                                 hipStream_t st, long long *n_win_out)
+{
+    const std::vector<int> &pos = g->host.pos;
+    std::vector<std::pair<long long, long long>> iv;
+    for (size_t i = 0; i < pos.size(); ++i) {
+        const long long lo = (long long)pos[i] - W + 1, hi = (long long)pos[i] + 1 + std::max(0, g->host.del_len[i]);
+        if (!iv.empty() && lo <= iv.back().second + 1) iv.back().second = std::max(iv.back().second, hi);
+        else iv.emplace_back(lo, hi);
+    }
+    if (g->call_pending) GX_TRY(hipEventSynchronize(g->ev_call));      // the last call's upload may still read h_vwins
+    g->h_vwins.clear();
+    const long long tail = g->dev.n_ins > 0 ? 1 : W;
+    for (int r = 0; r < n_regions; ++r) {
+        const long long s = std::max<long long>(h_starts[r], 0), e = std::min<long long>(h_stops[r], g->dev.ref_len);
+        const long long last = e - tail;
+        if (last < s) continue;
+        size_t k = (size_t)(std::lower_bound(iv.begin(), iv.end(), std::make_pair(s, LLONG_MIN),
+                                             [](const std::pair<long long, long long> &a, const std::pair<long long, long long> &b) {
+                                                 return a.second < b.first;
+                                             }) - iv.begin());
+        for (; k < iv.size() && iv[k].first <= last; ++k)
+            for (long long p = std::max(s, iv[k].first); p <= std::min(last, iv[k].second); ++p) {
+                g->h_vwins.push_back(p);
+                g->h_vwins.push_back(e);
+            }
+    }
+    if (unique && !g->h_vwins.empty()) {
+        static_assert(sizeof(VarWin) == 2 * sizeof(long long), "h_vwins holds (p, limit) pairs");
+        VarWin *b = reinterpret_cast<VarWin *>(g->h_vwins.data()), *e = b + g->h_vwins.size() / 2;
+        std::sort(b, e, [](const VarWin &x, const VarWin &y) { return x.p != y.p ? x.p < y.p : x.limit > y.limit; });
+        e = std::unique(b, e, [](const VarWin &x, const VarWin &y) { return x.p == y.p; });
+        g->h_vwins.resize(2 * (size_t)(e - b));
+    }
+    const long long n_win = (long long)(g->h_vwins.size() / 2);
+    *n_win_out = n_win;
+    if (n_win > 0) {
+        if ((size_t)n_win > g->v_cap) {
+            if (g->v_wins) GX_TRY(hipFree(g->v_wins));
+            g->v_wins = nullptr;
+            g->v_cap = 0;
+            GX_TRY(hipMalloc(&g->v_wins, sizeof(VarWin) * (size_t)n_win));
+            g->v_cap = (size_t)n_win;
+        }
+        GX_TRY(hipMemcpyAsync(g->v_wins, g->h_vwins.data(), sizeof(VarWin) * (size_t)n_win, hipMemcpyHostToDevice, st));
+    }
+    return GFM_OK;
+}
+
 GFM_API int gfm_graph_variant_effects(gfm_graph_t g, const gfm_motif_t *motifs, int32_t n_motifs, int32_t n_regions,
                                       const int64_t *h_starts, const int64_t *h_stops, uint32_t flags,
                                       uint64_t *const *d_keys, void *const *d_recs, const int64_t *rec_capacity,
@@ -200,43 +253,10 @@ GFM_API int gfm_graph_variant_effects(gfm_graph_t g, const gfm_motif_t *motifs, 
     }
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (const int rc = g->serialise(st)) return rc;
-    // ---- the windows within reach of a site: starts in [pos - W + 1, pos + 1 + del_len] (a walk that starts inside an insertion
-    // anchored at p - 1, on bases a deletion anchored before p removes), merged, cut to every region's window range
-    const std::vector<int> &pos = g->host.pos;
-    std::vector<std::pair<long long, long long>> iv;
-    for (size_t i = 0; i < pos.size(); ++i) {
-        const long long lo = (long long)pos[i] - W + 1, hi = (long long)pos[i] + 1 + std::max(0, g->host.del_len[i]);
-        if (!iv.empty() && lo <= iv.back().second + 1) iv.back().second = std::max(iv.back().second, hi);
-        else iv.emplace_back(lo, hi);
-    }
-    if (g->call_pending) GX_TRY(hipEventSynchronize(g->ev_call));      // the last call's upload may still read h_vwins
-    g->h_vwins.clear();
-    const long long tail = g->dev.n_ins > 0 ? 1 : W;
-    for (int r = 0; r < n_regions; ++r) {
-        const long long s = std::max<long long>(h_starts[r], 0), e = std::min<long long>(h_stops[r], g->dev.ref_len);
-        const long long last = e - tail;
-        if (last < s) continue;
-        size_t k = (size_t)(std::lower_bound(iv.begin(), iv.end(), std::make_pair(s, LLONG_MIN),
-                                             [](const std::pair<long long, long long> &a, const std::pair<long long, long long> &b) {
-                                                 return a.second < b.first;
-                                             }) - iv.begin());
-        for (; k < iv.size() && iv[k].first <= last; ++k)
-            for (long long p = std::max(s, iv[k].first); p <= std::min(last, iv[k].second); ++p) {
-                g->h_vwins.push_back(p);
-                g->h_vwins.push_back(e);
-            }
-    }
-    const long long n_win = (long long)(g->h_vwins.size() / 2);
+    long long n_win = 0;
+    if (const int rc = variant_stage_windows(g, W, n_regions, h_starts, h_stops, false, st, &n_win)) return rc;
     if (n_windows) *n_windows = n_win;
     if (n_win > 0) {
-        if ((size_t)n_win > g->v_cap) {
-            if (g->v_wins) GX_TRY(hipFree(g->v_wins));
-            g->v_wins = nullptr;
-            g->v_cap = 0;
-            GX_TRY(hipMalloc(&g->v_wins, sizeof(VarWin) * (size_t)n_win));
-            g->v_cap = (size_t)n_win;
-        }
-        GX_TRY(hipMemcpyAsync(g->v_wins, g->h_vwins.data(), sizeof(VarWin) * (size_t)n_win, hipMemcpyHostToDevice, st));
         const int grid = (int)std::min<long long>(n_win, 1 << 16);
         const int fwd = (flags & GFM_GRAPH_FORWARD_ONLY) ? 1 : 0, keep0 = (flags & GFM_VARIANT_KEEP_ZERO_FREQ) ? 1 : 0;
         const VarWin *wins = static_cast<const VarWin *>(g->v_wins);

@@ -2551,3 +2551,4 @@ inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 #include "gfm_graph_hapscores.hpp"
 #include "gfm_graph_hapaffinity.hpp"
 #include "gfm_graph_hit_alleles.hpp"
+#include "gfm_graph_variant_affinity.hpp"

@@ -686,6 +686,27 @@ int gfm_graph_haplotype_affinity(gfm_graph_t g, const gfm_motif_t *motifs, int32
                                  const int64_t *h_starts, const int64_t *h_stops, uint32_t flags, uint64_t *const *d_sums,
                                  int32_t *d_overflow, int32_t windows_per_run, int32_t haplotypes_per_block, void *stream);
 
+/* ------------------------------------------------------------------ per-variant affinity effects (sums, exact)
+ * For every graph site s and allele a of it (0 = none of the site's ALTs), slot = s * 4 + a: sum = the sum of w[score] over
+ * every k-mer of every haplotype's own sequence, once per strand (one strand with GFM_GRAPH_FORWARD_ONLY), that lies in at
+ * least one region under the report's region rule and whose bases cover the footprint of (s, a) -- the footprints of
+ * gfm_graph_variant_effects --, and rows = the number of those k-mers; a k-mer that several regions hold counts once.  On
+ * the device every walk of every distinct window start adds carriers * (w[s+] + w[s-]) and carriers * strands to the slots
+ * of its constraints, carriers = the popcount over all bitset words of the AND of the constraints' bitsets.  w =
+ * d_weights[m], uint64 [table_len of motif m] on the device, indexed by the scaled score (a k-mer holding N scores the
+ * motif's min_val), taken as given.  Per motif m, d_sums[m] uint64 [4 * n_sites][2] (sum, rows), zeroed by the caller.
+ * Integer adds: the result is exact and depends neither on table_entries nor on the order of the device's atomics.
+ * *d_overflow (zeroed by the caller): bit 0 = a window holds more than 2^24 walks (left out: the sums are not complete),
+ * bit 1 = a 64-bit add wrapped (every add, in LDS and in global memory, is checked: old + v < v).  *n_windows (host,
+ * optional) = the distinct window starts enumerated.  table_entries (0: 64, else a power of two up to 64): the entries of
+ * a wavefront's LDS staging table; an add that finds it full goes to global memory.  GFM_ERR_INVALID when the graph carries
+ * no haplotypes.  Motifs of ONE width.  Enqueue only (host work: the window list; the handle's calls are serialised as
+ * gfm_graph_score's are). */
+int gfm_graph_variant_affinity(gfm_graph_t g, const gfm_motif_t *motifs, int32_t n_motifs, const uint64_t *const *d_weights,
+                               int32_t n_regions, const int64_t *h_starts, const int64_t *h_stops, uint32_t flags,
+                               uint64_t *const *d_sums, int32_t *d_overflow, int64_t *n_windows, int32_t table_entries,
+                               void *stream);
+
 /* ------------------------------------------------------------------ hit pairs: rows close to each other that share carriers
  * Graph-independent (csrc/hit_pairs.hip).  n rows (n < 2^31 - 1) in device memory, in ascending (d_group, d_lo) order:
  * d_group int32, d_lo <= d_hi int64 (|x| < 2^61), d_masks uint64 [n][hw] (hw >= 1 words of a bitset whose unused tail
