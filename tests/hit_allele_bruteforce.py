@@ -15,7 +15,7 @@ import numpy as np
 
 from extract_helpers import motif_as_oracle_dict
 from haplotype_bruteforce import integer_cutoff
-from variant_bruteforce import int_score, revcomp, spell
+from variant_bruteforce import haplotype_classes, int_score, revcomp, spell
 from variant_walks import _carriers, window_walks
 
 
@@ -37,8 +37,9 @@ def region_name(idx, region, chrom=None):
     return f"{chrom or idx.chrom}:{region[0]}-{region[1]}"
 
 
-def carrier_counts(idx, regions, W, sm, min_val, cutoff, forward_only=False, chrom=None):
-    """-> {(region name, start, stop, strand, k-mer as printed): int64 [H] rows of haplotype h with that key}"""
+def carrier_counts(idx, regions, W, sm, min_val, cutoff, forward_only=False, chrom=None, memo=False):
+    """-> {(region name, start, stop, strand, k-mer as printed): int64 [H] rows of haplotype h with that key}.  `memo`: one
+    haplotype per class of variant_bruteforce.haplotype_classes, its counts copied to the class (the same result)."""
     sm = np.asarray(sm, dtype=np.int64)
     H = int(idx.n_haplotypes) if idx.alt_bits is not None else 0
     L = len(idx.ref)
@@ -51,7 +52,8 @@ def carrier_counts(idx, regions, W, sm, min_val, cutoff, forward_only=False, chr
             s = cache[k] = int_score(k, sm, min_val)
         return s
 
-    for h in range(H):
+    first, cls = haplotype_classes(idx) if memo else (np.arange(H), np.arange(H))
+    for c, h in enumerate(first.tolist()):
         seq, coord, ins, _, _ = spell(idx, h)
         for o in range(0, len(seq) - W + 1):
             start = coord[o] + (1 if ins[o] else 0)
@@ -68,9 +70,9 @@ def carrier_counts(idx, regions, W, sm, min_val, cutoff, forward_only=False, chr
                     key = (region_name(idx, (S, E), chrom), a, b, strand, printed.decode())
                     v = out.get(key)
                     if v is None:
-                        v = out[key] = np.zeros(H, dtype=np.int64)
-                    v[h] += 1
-    return out
+                        v = out[key] = np.zeros(len(first), dtype=np.int64)
+                    v[c] += 1
+    return {key: v[cls] for key, v in out.items()}
 
 
 def walk_rows(idx, regions, W, sm, min_val, cutoff, forward_only=False, recomb=False, chrom=None):
@@ -146,11 +148,11 @@ def check_first_principles(ha, idx, groups=None):
     return car
 
 
-def check_against_haplotypes(ha, car, idx, regions, motif, cutoff, forward_only, chrom=None):
+def check_against_haplotypes(ha, car, idx, regions, motif, cutoff, forward_only, chrom=None, memo=False):
     """check 2: per key the sum over the table's rows of the carrier bits equals the haplotype brute force's count, and the
     keys of the rows with carriers are exactly its keys"""
     od = motif_as_oracle_dict(motif)
-    exp = carrier_counts(idx, regions, od["width"], od["score_matrix"], od["min_val"], cutoff, forward_only, chrom)
+    exp = carrier_counts(idx, regions, od["width"], od["score_matrix"], od["min_val"], cutoff, forward_only, chrom, memo=memo)
     got = {}
     rep = ha.report
     for r, (name, a, b, strand, seq, f) in enumerate(zip(rep["sequence_name"], rep["start"], rep["stop"], rep["strand"],
@@ -183,11 +185,11 @@ def check_against_walks(ha, idx, regions, motif, cutoff, forward_only, recomb, c
     return sum(exp.values())
 
 
-def check_table(ha, idx, regions, motif, args, groups=None, chrom=None):
-    """checks 2, 3 and 4 of one table (made with carriers=True) -> (rows, keys)"""
+def check_table(ha, idx, regions, motif, args, groups=None, chrom=None, memo=False):
+    """checks 2, 3 and 4 of one table (made with carriers=True) -> (rows, keys); `memo` goes to carrier_counts"""
     car = check_first_principles(ha, idx, groups)
     cutoff = report_cutoff(motif, args, ha.report)
-    keys = check_against_haplotypes(ha, car, idx, regions, motif, cutoff, args.noreverse, chrom)
+    keys = check_against_haplotypes(ha, car, idx, regions, motif, cutoff, args.noreverse, chrom, memo=memo)
     rows = check_against_walks(ha, idx, regions, motif, cutoff, args.noreverse, args.recomb, chrom)
     assert rows == len(ha)
     return rows, keys

@@ -15,7 +15,7 @@ import numpy as np
 
 from extract_helpers import motif_as_oracle_dict
 from hit_allele_bruteforce import report_cutoff, unpack, walk_rows
-from variant_bruteforce import int_score, revcomp, spell
+from variant_bruteforce import haplotype_classes, int_score, revcomp, spell
 from variant_walks import _carriers
 
 
@@ -76,8 +76,9 @@ def _listings(entries):
     return out
 
 
-def _count_pairs(out, listing, keys, lo, hi, min_gap, max_gap):
-    """the pairs i < j of the instances within the gap into out[(listing, key, key)] (the smaller key first)"""
+def _count_pairs(out, listing, keys, lo, hi, min_gap, max_gap, times=1):
+    """the pairs i < j of the instances within the gap into out[(listing, key, key)] (the smaller key first), each counted
+    `times` times"""
     n = len(keys)
     if n < 2:
         return
@@ -91,12 +92,13 @@ def _count_pairs(out, listing, keys, lo, hi, min_gap, max_gap):
     codes, counts = np.unique(kid[i] * len(names) + kid[j], return_counts=True)
     for code, c in zip(codes.tolist(), counts.tolist()):
         a, b = names[code // len(names)], names[code % len(names)]
-        out[(listing,) + ((a, b) if a <= b else (b, a))] += c
+        out[(listing,) + ((a, b) if a <= b else (b, a))] += c * times
 
 
-def haplotype_pairs(entries, motifs, cutoffs, min_gap, max_gap, forward_only=False):
+def haplotype_pairs(entries, motifs, cutoffs, min_gap, max_gap, forward_only=False, memo=False):
     """-> Counter {(listing, key, key): over the haplotypes, the pairs of distinct row instances of the listing within the
-    gap with these two keys (the smaller first)}"""
+    gap with these two keys (the smaller first)}.  `memo`: one haplotype per class of variant_bruteforce.haplotype_classes,
+    counted as many times as the class has haplotypes (the same result)."""
     out = Counter()
     ods = [motif_as_oracle_dict(m) for m in motifs]
     cache = [{} for _ in motifs]
@@ -111,7 +113,12 @@ def haplotype_pairs(entries, motifs, cutoffs, min_gap, max_gap, forward_only=Fal
         mine = [x for x in _listings(entries) if x[1] is idx]
         H = int(idx.n_haplotypes) if idx.alt_bits is not None else 0
         L = len(idx.ref)
-        for h in range(H):
+        if memo:
+            first, cls = haplotype_classes(idx)
+            todo = list(zip(first.tolist(), np.bincount(cls, minlength=len(first)).tolist()))
+        else:
+            todo = [(h, 1) for h in range(H)]
+        for h, times in todo:
             seq, coord, ins, _, _ = spell(idx, h)
             inst = []                                          # (start of '+', stop of '+', key)
             for m, od in enumerate(ods):
@@ -129,7 +136,7 @@ def haplotype_pairs(entries, motifs, cutoffs, min_gap, max_gap, forward_only=Fal
             for listing, _, S, E in mine:
                 sel = [x for x in inst if max(S, 0) <= x[0] < min(E, L) and x[1] <= min(E, L)]
                 _count_pairs(out, listing, [x[2] for x in sel], [min(x[0], x[1]) for x in sel], [max(x[0], x[1]) for x in sel],
-                             min_gap, max_gap)
+                             min_gap, max_gap, times)
     return out
 
 
@@ -180,9 +187,9 @@ def table_rows(hp):
             np.concatenate(masks, axis=0), np.concatenate(ref))
 
 
-def check_pairs(hp, entries, motifs, args, min_gap, max_gap, groups=None, chrom_names=None):
+def check_pairs(hp, entries, motifs, args, min_gap, max_gap, groups=None, chrom_names=None, memo=False):
     """every check of one HitPairs -> the number of pairs.  entries: [(GraphIndex, regions)] in the caller's order; groups:
-    {name: [haplotype columns]} or None"""
+    {name: [haplotype columns]} or None; `memo` goes to haplotype_pairs"""
     P = len(hp)
     H = int(entries[0][0].n_haplotypes)
     motif, row, listing, lo, hi, masks, ref = table_rows(hp)
@@ -225,7 +232,7 @@ def check_pairs(hp, entries, motifs, args, min_gap, max_gap, groups=None, chrom_
     assert np.array_equal(ea, ia) and np.array_equal(eb, ib) and np.array_equal(ej, hp.co_haplotypes)
     # the haplotype brute force: per key pair the sum of co_haplotypes is the number of instance pairs over the haplotypes
     cutoffs = [report_cutoff(m, args, t.report) for m, t in zip(motifs, hp.tables)]
-    exp = haplotype_pairs(entries, motifs, cutoffs, min_gap, max_gap, args.noreverse)
+    exp = haplotype_pairs(entries, motifs, cutoffs, min_gap, max_gap, args.noreverse, memo=memo)
     got = Counter()
     cols = [(t.report["start"].tolist(), t.report["stop"].tolist(), t.report["strand"].tolist(),
              t.report["matched_sequence"].tolist()) for t in hp.tables]

@@ -1,7 +1,9 @@
 """Hit-linkage table on the GPU.  Kernel level: grafimo_amd.hit_linkage.link_rows (gfm_hit_linkage) against the numpy /
 Python restatement of its contract on synthetic rows; end to end: compute_hit_linkage through check_linkage
 (tests/hit_linkage_bruteforce.py), the manifest route and the CLI.  Every comparison is exact but check_linkage's one
-against np.corrcoef."""
+against np.corrcoef.
+The width sweep sits on every staging step of link_kernel (2^logWC words, logWC 0 .. 4): 300 haplotypes are 5 words (logWC 3,
+a partial step), 512 are 8 (a full step of 8), 1 024 are 16 (one full step of 16, no tail mask), 1 025 are 17 (16 + 1)."""
 import contextlib
 import ctypes
 import functools
@@ -49,7 +51,7 @@ def _same(got, exp):
 
 
 # 1100 haplotypes are 18 words: one full staging step of 16 words and one of 2; 5096 are 80: five steps
-@pytest.mark.parametrize("H", [1, 2, 63, 64, 65, 200, 1100, 5096])
+@pytest.mark.parametrize("H", [1, 2, 63, 64, 65, 200, 300, 512, 1024, 1025, 1100, 5096])
 def test_link_rows_equals_the_reference_at_every_bitset_width(H):
     from grafimo_amd.hit_linkage import link_rows
     for flank, min_r2 in CUTS:

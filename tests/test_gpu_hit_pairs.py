@@ -1,6 +1,10 @@
 """Hit-pair table on the GPU.  Kernel level: grafimo_amd.hit_pairs.pair_rows (gfm_hit_pairs) against the O(n^2) numpy
 restatement of its contract; end to end: compute_hit_pairs against the haplotype brute force and first principles
-(tests/hit_pair_bruteforce.py), the manifest route and the CLI.  Every comparison is exact."""
+(tests/hit_pair_bruteforce.py), the manifest route and the CLI.  Every comparison is exact.
+The width sweep sits on every sub-group width of pair_kernel (L = 1 .. 64 lanes a row): 130 haplotypes are 3 words (L = 4, a
+lane idle), 300 are 5 (L = 8), 1 000 are 16 (= L), 1 100 are 18 (L = 32, the second register word partly used), 2 100 are 33
+(L = 64), 8 192 are 128 (= 2 L, the last row kept in registers), 8 193 are 129 (the first read from memory), 12 345 are 193
+(three full turns of the word loop and a partial one)."""
 import contextlib
 import ctypes
 import io
@@ -47,7 +51,7 @@ def _same(got, exp):
     return len(exp[0])
 
 
-@pytest.mark.parametrize("H", [1, 63, 64, 65, 200, 5096])
+@pytest.mark.parametrize("H", [1, 63, 64, 65, 130, 200, 300, 1000, 1100, 2100, 5096, 8192, 8193, 12345])
 @pytest.mark.parametrize("G", [0, 5])
 def test_pair_rows_equals_the_reference_at_every_bitset_width(H, G):
     from grafimo_amd.hit_pairs import pair_rows
