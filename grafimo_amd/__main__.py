@@ -112,7 +112,7 @@ def get_parser():
                         "haplotype's total binding affinity -- the sum of 2^(log-odds / T) over every k-mer of its own "
                         "sequence --, beside the reference's (graph routes only)")
     p.add_argument("--affinity-temperature", dest="affinity_temperature", type=float, default=None, metavar="T",
-                   help="with --haplotype-affinity or --variant-affinity: the temperature T > 0 the log-odds scores are "
+                   help="with --haplotype-affinity, --variant-affinity or --haplotype-classes: the temperature T > 0 the log-odds scores are "
                         "divided by; default 1")
     p.add_argument("--variant-affinity", action="store_true", dest="variant_affinity",
                    help="also write grafimo_variant_affinity[_MOTIF].tsv (printed with -f): per variant, the log2 of the mean "
@@ -124,8 +124,15 @@ def get_parser():
                    help="also write grafimo_hit_alleles[_MOTIF].tsv (printed with -f): the report's rows, each with the variant "
                         "alleles that make its k-mer and, with --haplotype-groups, its carriers per group (graph routes only)")
     p.add_argument("--haplotype-groups", dest="haplotype_groups", metavar="FILE",
-                   help="with --hit-alleles or --hit-pairs: SAMPLE GROUP lines (the 1000 Genomes panel file reads as is), one "
+                   help="with --hit-alleles, --hit-pairs or --haplotype-classes: SAMPLE GROUP lines (the 1000 Genomes panel file reads as is), one "
                         "haplotypes_GROUP column per group")
+    p.add_argument("--haplotype-classes", action="store_true", dest="haplotype_classes",
+                   help="also write grafimo_haplotype_classes[_MOTIF].tsv (printed with -f) and "
+                        "grafimo_haplotype_class_members.tsv: per region the distinct allele combinations the haplotypes hold, "
+                        "each with its count, its counts per --haplotype-groups group, its alleles and its representative's "
+                        "best score and total affinity (--affinity-temperature) (graph routes only)")
+    p.add_argument("--class-min-haplotypes", dest="class_min_haplotypes", type=int, default=None, metavar="N",
+                   help="with --haplotype-classes: keep only the classes of at least N haplotypes; default 1")
     p.add_argument("--hit-pairs", action="store_true", dest="hit_pairs",
                    help="also write grafimo_hit_pairs.tsv (printed with -f): the pairs of report rows -- of one motif or of "
                         "two -- of a region that lie within --pair-gap of each other and share carrier haplotypes, with how "
@@ -201,7 +208,8 @@ def buildvg(argv):
 _GRAPH_TABLES = {"variant_effects": ("--variant-effects", "alleles"), "haplotype_hits": ("--haplotype-hits", "walks"),
                  "haplotype_scores": ("--haplotype-scores", "walks"), "haplotype_affinity": ("--haplotype-affinity", "walks"),
                  "variant_affinity": ("--variant-affinity", "walks"), "hit_alleles": ("--hit-alleles", "walks"),
-                 "hit_pairs": ("--hit-pairs", "walks"), "hit_linkage": ("--hit-linkage", "walks")}
+                 "hit_pairs": ("--hit-pairs", "walks"), "hit_linkage": ("--hit-linkage", "walks"),
+                 "haplotype_classes": ("--haplotype-classes", "haplotypes")}
 
 
 def _graph_only(a, table):
@@ -239,8 +247,8 @@ def main(argv=None):
                  "threshold (drop --qvalueT)")
     _graph_only(a, "haplotype_hits")
     _graph_only(a, "haplotype_scores")
-    if a.affinity_temperature is not None and not (a.haplotype_affinity or a.variant_affinity):
-        sys.exit("ERROR: --affinity-temperature goes with --haplotype-affinity or --variant-affinity")
+    if a.affinity_temperature is not None and not (a.haplotype_affinity or a.variant_affinity or a.haplotype_classes):
+        sys.exit("ERROR: --affinity-temperature goes with --haplotype-affinity or --variant-affinity or --haplotype-classes")
     if a.affinity_temperature is not None and not a.affinity_temperature > 0:
         sys.exit(f"ERROR: --affinity-temperature {a.affinity_temperature} is not > 0")
     _graph_only(a, "haplotype_affinity")
@@ -249,8 +257,13 @@ def main(argv=None):
     if a.variant_affinity_delta is not None and not a.variant_affinity_delta >= 0:
         sys.exit(f"ERROR: --variant-affinity-delta {a.variant_affinity_delta} is not >= 0")
     _graph_only(a, "variant_affinity")
-    if a.haplotype_groups and not (a.hit_alleles or a.hit_pairs):
-        sys.exit("ERROR: --haplotype-groups goes with --hit-alleles or --hit-pairs")
+    if a.haplotype_groups and not (a.hit_alleles or a.hit_pairs or a.haplotype_classes):
+        sys.exit("ERROR: --haplotype-groups goes with --hit-alleles or --hit-pairs or --haplotype-classes")
+    if a.class_min_haplotypes is not None and not a.haplotype_classes:
+        sys.exit("ERROR: --class-min-haplotypes goes with --haplotype-classes")
+    if a.class_min_haplotypes is not None and a.class_min_haplotypes < 1:
+        sys.exit(f"ERROR: --class-min-haplotypes {a.class_min_haplotypes} < 1")
+    _graph_only(a, "haplotype_classes")
     if a.pair_gap is not None and not a.hit_pairs:
         sys.exit("ERROR: --pair-gap goes with --hit-pairs")
     if a.pair_gap is not None and a.pair_gap[0] > a.pair_gap[1]:
@@ -394,6 +407,18 @@ def main(argv=None):
                                       flank=10000 if a.linkage_flank is None else a.linkage_flank,
                                       min_r2=0.8 if a.linkage_r2 is None else a.linkage_r2),
              write_hit_linkage, print_hit_linkage, lambda hl: f"{len(hl)} hit linkage rows")
+    if a.haplotype_classes:                            # (the classes once per call, a table per motif)
+        from .haplotype_classes import (compute_haplotype_class_table_many, compute_haplotype_classes, print_haplotype_classes,
+                                        write_haplotype_class_members, write_haplotype_classes)
+        graph, regions, first_index = source("haplotype_classes")
+        hc = compute_haplotype_classes(graph, regions, a.debug, wf, haplotype_groups=groups(first_index))
+        emit(compute_haplotype_class_table_many(motifs, graph, regions, a.debug, wf,
+                                                temperature=1.0 if a.affinity_temperature is None else a.affinity_temperature,
+                                                min_haplotypes=a.class_min_haplotypes or 1, classes=hc),
+             write_haplotype_classes, print_haplotype_classes, lambda t: f"{len(t)} haplotype class rows")
+        if not a.text_only:
+            print(f"{hc.class_of.shape[0]} x {hc.class_of.shape[1]} haplotype class members written to "
+                  f"{write_haplotype_class_members(hc, wf)}")
     if sequences_loc:
         import shutil
         shutil.rmtree(sequences_loc, ignore_errors=True)

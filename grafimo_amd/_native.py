@@ -147,6 +147,10 @@ PROTOTYPES = {
                                              ctypes.c_uint32, c_void_p, c_void_p, c_i32, c_i32, c_void_p]),
     "gfm_graph_variant_affinity": (c_int, [c_void_p, c_void_p, c_i32, c_void_p, c_i32, c_void_p, c_void_p, ctypes.c_uint32,
                                            c_void_p, c_void_p, P(c_i64), c_i32, c_void_p]),
+    "gfm_graph_haplotype_classes": (c_int, [c_void_p, c_i32, c_void_p, c_void_p, ctypes.c_uint64, c_i32, c_i32, c_void_p, c_void_p,
+                                            c_void_p, c_i64, c_void_p]),
+    "gfm_graph_haplotype_class_records": (c_int, [c_i32, c_i32, c_void_p, c_void_p, c_void_p, c_i32, c_void_p, c_void_p, c_void_p,
+                                                  c_void_p]),
     "gfm_hit_pairs": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_i32, c_i64, c_i64, c_i32, c_void_p, c_void_p, c_i64,
                               c_void_p, c_void_p, c_void_p, ctypes.c_uint32, P(c_i64), c_void_p]),
     "gfm_hit_linkage": (c_int, [c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_i64, c_i32, c_i32, c_i64,

@@ -1307,6 +1307,7 @@ struct gfm_graph {
     std::vector<long long> h_vwins;
     void *v_wins = nullptr;
     size_t v_cap = 0;
+    Buf<unsigned char> hc_buf;           // gfm_graph_haplotype_classes: region records, keys, representatives, spill tables
     bool call_pending = false;
     int serialise(hipStream_t st)
     {
@@ -1538,6 +1539,7 @@ GFM_API void gfm_graph_destroy(gfm_graph_t g)
     g->plan = nullptr;
     g->f_slabs.release();
     if (g->v_wins) (void)hipFree(g->v_wins);
+    g->hc_buf.release();
     delete g;
 }
 
@@ -2552,3 +2554,4 @@ inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 #include "gfm_graph_hapaffinity.hpp"
 #include "gfm_graph_hit_alleles.hpp"
 #include "gfm_graph_variant_affinity.hpp"
+#include "gfm_graph_hapclasses.hpp"

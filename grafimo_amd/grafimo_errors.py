@@ -43,3 +43,8 @@ class VGError(GrafimoError):
 
 class FileFormatError(GrafimoError):
     pass
+
+
+class HashCollisionError(GrafimoError):
+    """haplotype_classes: two allele combinations shared a key under every seed tried (the classes are verified, never
+    silently wrong)"""

@@ -501,7 +501,9 @@ int gfm_graph_score_multi(gfm_graph_t g, const gfm_motif_t *motifs, int32_t n_mo
                           void *stream);
 /* Measurement aid (bench.py `extract.roofline`): with on != 0 the next (up to 64) gfm_graph_score[_multi] calls bracket
  * graph_score_kernel ALONE -- the kernel of the plain and one-deletion windows, the one the fused path's time is in -- with
- * a hipEvent pair on the launch stream; gfm_graph_profile_read waits for them and returns the durations in ms, oldest first. */
+ * a hipEvent pair on the launch stream; gfm_graph_profile_read waits for them and returns the durations in ms, oldest first.
+ * gfm_graph_haplotype_classes brackets every launch of its own the same way, in launch order: per chunk of regions the key
+ * kernel, the class kernel, one launch per batch of spilled regions, the verify kernel (scripts/classes_probe.py). */
 int gfm_graph_profile_enable(gfm_graph_t g, int on);
 int gfm_graph_profile_read(gfm_graph_t g, float *h_ms_out, int capacity, int *n_out);
 int gfm_graph_annotate(gfm_graph_t g, const void *d_hits, const uint64_t *d_hit_count, int64_t hit_capacity,
@@ -706,6 +708,34 @@ int gfm_graph_variant_affinity(gfm_graph_t g, const gfm_motif_t *motifs, int32_t
                                int32_t n_regions, const int64_t *h_starts, const int64_t *h_stops, uint32_t flags,
                                uint64_t *const *d_sums, int32_t *d_overflow, int64_t *n_windows, int32_t table_entries,
                                void *stream);
+
+/* ------------------------------------------------------------------ haplotype classes: distinct allele combinations per region
+ * The sites of region [S, E) clipped to the chromosome, T(r): a substitution with S <= pos < E, an insertion with
+ * S - 1 <= pos < E, a deletion of d bases with pos + 1 < E and pos + d >= S (the report's region rule: a row starts in [S, E)
+ * and stops <= E); an empty region has none.  The state of a haplotype at a site is its bits in the site's n_alts used slots
+ * (0: none of the ALTs); two haplotypes are in one class of r when their states agree on T(r).  Classes are numbered per
+ * region by count descending, then by smallest member.  d_class int32 [n_regions][n_hap] receives the class of every
+ * haplotype, d_n_classes int32 [n_regions] the number of classes.  Grouping is by a 64-bit Zobrist key (seed: any value;
+ * key_bits 1 .. 64 truncates it, a lab knob) and VERIFIED: every haplotype is compared with its class's smallest member at
+ * every site of T(r), and bit 0 of *d_status (cleared by the caller) is set when two allele combinations shared a key -- the
+ * classes are then wrong and the call is repeated with another seed; with *d_status == 0 they are exact.  table_slots: the
+ * slots of a region's LDS table, 0 (2048) or a power of two in [64, 2048]; a region of more than 3/4 of it classes is
+ * redone over a table in global memory; the result does not depend on it.  scratch_bytes (0: 256 MB) bounds the keys and
+ * tables: the regions go through in chunks (one region's worth is always taken); the result does not depend on it.
+ * At most 2^20 haplotypes.  GFM_ERR_INVALID for a graph without haplotypes, h_stops[r] < h_starts[r] and bad knobs.  Waits
+ * for the stream (the list of spilled regions is read on the host); the handle's calls are serialised as gfm_graph_score's. */
+int gfm_graph_haplotype_classes(gfm_graph_t g, int32_t n_regions, const int64_t *h_starts, const int64_t *h_stops, uint64_t seed,
+                                int32_t key_bits, int32_t table_slots, int32_t *d_class, int32_t *d_n_classes, int32_t *d_status,
+                                int64_t scratch_bytes, void *stream);
+
+/* Graph-independent: the records of the classes of a class matrix.  d_class int32 [n_regions][n_hap] with 0 <= class <
+ * d_class_off[r + 1] - d_class_off[r] (other values are left out), d_class_off int64 [n_regions + 1] the exclusive scan of
+ * the class counts, optionally d_group_bits uint64 [n_groups][ceil(n_hap / 64)], n_groups 0 .. 64.  Per class k of region r at
+ * d_class_off[r] + k: d_count int32 (its haplotypes), d_first int32 (its smallest member) and d_group_counts int32 [n_groups]
+ * (its haplotypes per group); the outputs are initialised here.  Enqueue only. */
+int gfm_graph_haplotype_class_records(int32_t n_regions, int32_t n_hap, const int32_t *d_class, const int64_t *d_class_off,
+                                      const uint64_t *d_group_bits, int32_t n_groups, int32_t *d_count, int32_t *d_first,
+                                      int32_t *d_group_counts, void *stream);
 
 /* ------------------------------------------------------------------ hit pairs: rows close to each other that share carriers
  * Graph-independent (csrc/hit_pairs.hip).  n rows (n < 2^31 - 1) in device memory, in ascending (d_group, d_lo) order:
