@@ -124,7 +124,7 @@ def get_parser():
                    help="also write grafimo_hit_alleles[_MOTIF].tsv (printed with -f): the report's rows, each with the variant "
                         "alleles that make its k-mer and, with --haplotype-groups, its carriers per group (graph routes only)")
     p.add_argument("--haplotype-groups", dest="haplotype_groups", metavar="FILE",
-                   help="with --hit-alleles, --hit-pairs or --haplotype-classes: SAMPLE GROUP lines (the 1000 Genomes panel file reads as is), one "
+                   help="with --hit-alleles, --hit-pairs, --haplotype-classes or --haplotype-sequences: SAMPLE GROUP lines (the 1000 Genomes panel file reads as is), one "
                         "haplotypes_GROUP column per group")
     p.add_argument("--haplotype-classes", action="store_true", dest="haplotype_classes",
                    help="also write grafimo_haplotype_classes[_MOTIF].tsv (printed with -f) and "
@@ -133,6 +133,11 @@ def get_parser():
                         "best score and total affinity (--affinity-temperature) (graph routes only)")
     p.add_argument("--class-min-haplotypes", dest="class_min_haplotypes", type=int, default=None, metavar="N",
                    help="with --haplotype-classes: keep only the classes of at least N haplotypes; default 1")
+    p.add_argument("--haplotype-sequences", action="store_true", dest="haplotype_sequences",
+                   help="also write grafimo_haplotype_sequences.fa and grafimo_haplotype_sequence_versions.tsv (the table is "
+                        "printed with -f): per region the distinct sequences the haplotypes spell in it, each with its count, "
+                        "its counts per --haplotype-groups group, the haplotype classes that spell it and its bases "
+                        "(graph routes only)")
     p.add_argument("--hit-pairs", action="store_true", dest="hit_pairs",
                    help="also write grafimo_hit_pairs.tsv (printed with -f): the pairs of report rows -- of one motif or of "
                         "two -- of a region that lie within --pair-gap of each other and share carrier haplotypes, with how "
@@ -209,7 +214,8 @@ _GRAPH_TABLES = {"variant_effects": ("--variant-effects", "alleles"), "haplotype
                  "haplotype_scores": ("--haplotype-scores", "walks"), "haplotype_affinity": ("--haplotype-affinity", "walks"),
                  "variant_affinity": ("--variant-affinity", "walks"), "hit_alleles": ("--hit-alleles", "walks"),
                  "hit_pairs": ("--hit-pairs", "walks"), "hit_linkage": ("--hit-linkage", "walks"),
-                 "haplotype_classes": ("--haplotype-classes", "haplotypes")}
+                 "haplotype_classes": ("--haplotype-classes", "haplotypes"),
+                 "haplotype_sequences": ("--haplotype-sequences", "haplotypes")}
 
 
 def _graph_only(a, table):
@@ -257,13 +263,15 @@ def main(argv=None):
     if a.variant_affinity_delta is not None and not a.variant_affinity_delta >= 0:
         sys.exit(f"ERROR: --variant-affinity-delta {a.variant_affinity_delta} is not >= 0")
     _graph_only(a, "variant_affinity")
-    if a.haplotype_groups and not (a.hit_alleles or a.hit_pairs or a.haplotype_classes):
-        sys.exit("ERROR: --haplotype-groups goes with --hit-alleles or --hit-pairs or --haplotype-classes")
+    if a.haplotype_groups and not (a.hit_alleles or a.hit_pairs or a.haplotype_classes or a.haplotype_sequences):
+        sys.exit("ERROR: --haplotype-groups goes with --hit-alleles or --hit-pairs or --haplotype-classes or "
+                 "--haplotype-sequences")
     if a.class_min_haplotypes is not None and not a.haplotype_classes:
         sys.exit("ERROR: --class-min-haplotypes goes with --haplotype-classes")
     if a.class_min_haplotypes is not None and a.class_min_haplotypes < 1:
         sys.exit(f"ERROR: --class-min-haplotypes {a.class_min_haplotypes} < 1")
     _graph_only(a, "haplotype_classes")
+    _graph_only(a, "haplotype_sequences")
     if a.pair_gap is not None and not a.hit_pairs:
         sys.exit("ERROR: --pair-gap goes with --hit-pairs")
     if a.pair_gap is not None and a.pair_gap[0] > a.pair_gap[1]:
@@ -407,6 +415,7 @@ def main(argv=None):
                                       flank=10000 if a.linkage_flank is None else a.linkage_flank,
                                       min_r2=0.8 if a.linkage_r2 is None else a.linkage_r2),
              write_hit_linkage, print_hit_linkage, lambda hl: f"{len(hl)} hit linkage rows")
+    hc = None
     if a.haplotype_classes:                            # (the classes once per call, a table per motif)
         from .haplotype_classes import (compute_haplotype_class_table_many, compute_haplotype_classes, print_haplotype_classes,
                                         write_haplotype_class_members, write_haplotype_classes)
@@ -419,6 +428,17 @@ def main(argv=None):
         if not a.text_only:
             print(f"{hc.class_of.shape[0]} x {hc.class_of.shape[1]} haplotype class members written to "
                   f"{write_haplotype_class_members(hc, wf)}")
+    if a.haplotype_sequences:                          # (motif-independent: once per call; the classes of --haplotype-classes serve)
+        from .haplotype_sequences import (compute_haplotype_sequences, haplotype_sequence_paths, print_haplotype_sequence_versions,
+                                          write_haplotype_sequence_versions, write_haplotype_sequences_fasta)
+        graph, regions, first_index = source("haplotype_sequences")
+        hs = compute_haplotype_sequences(graph, regions, a.debug, wf, haplotype_groups=groups(first_index), classes=hc)
+        if a.text_only:                                # -f: printed like the report, no file written
+            print_haplotype_sequence_versions(hs)
+        else:
+            fasta, tsv = haplotype_sequence_paths(wf)
+            print(f"{len(hs)} haplotype sequences written to {write_haplotype_sequences_fasta(hs, fasta)}")
+            print(f"{len(hs)} haplotype sequence versions written to {write_haplotype_sequence_versions(hs, tsv)}")
     if sequences_loc:
         import shutil
         shutil.rmtree(sequences_loc, ignore_errors=True)

@@ -36,6 +36,7 @@ GFM_VARIANT_ALL_SITES = 1
 GFM_VARIANT_KEEP_ZERO_FREQ = 2
 GFM_PAIRS_HAVE_OFFSETS = 1
 GFM_LINKAGE_HAVE_OFFSETS = 1
+GFM_SEQS_HAVE_LENGTHS = 1
 ABI_VERSION = 12
 RANGE = 1000
 
@@ -151,6 +152,9 @@ PROTOTYPES = {
                                             c_void_p, c_i64, c_void_p]),
     "gfm_graph_haplotype_class_records": (c_int, [c_i32, c_i32, c_void_p, c_void_p, c_void_p, c_i32, c_void_p, c_void_p, c_void_p,
                                                   c_void_p]),
+    "gfm_graph_haplotype_sequences": (c_int, [c_void_p, c_i32, c_void_p, c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_void_p, c_i64,
+                                              c_void_p, c_void_p, ctypes.c_uint64, c_i32, c_void_p, ctypes.c_uint32, P(c_i64), c_void_p]),
+    "gfm_sequences_verify": (c_int, [c_i64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "gfm_hit_pairs": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_i32, c_i64, c_i64, c_i32, c_void_p, c_void_p, c_i64,
                               c_void_p, c_void_p, c_void_p, ctypes.c_uint32, P(c_i64), c_void_p]),
     "gfm_hit_linkage": (c_int, [c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_i64, c_i32, c_i32, c_i64,

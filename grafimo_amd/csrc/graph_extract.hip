@@ -1308,6 +1308,7 @@ struct gfm_graph {
     void *v_wins = nullptr;
     size_t v_cap = 0;
     Buf<unsigned char> hc_buf;           // gfm_graph_haplotype_classes: region records, keys, representatives, spill tables
+    Buf<unsigned char> hseq_buf;           // gfm_graph_haplotype_sequences: region records, the status word and the total
     bool call_pending = false;
     int serialise(hipStream_t st)
     {
@@ -1540,6 +1541,7 @@ GFM_API void gfm_graph_destroy(gfm_graph_t g)
     g->f_slabs.release();
     if (g->v_wins) (void)hipFree(g->v_wins);
     g->hc_buf.release();
+    g->hseq_buf.release();
     delete g;
 }
 
@@ -2555,3 +2557,4 @@ inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 #include "gfm_graph_hit_alleles.hpp"
 #include "gfm_graph_variant_affinity.hpp"
 #include "gfm_graph_hapclasses.hpp"
+#include "gfm_graph_hapsequences.hpp"

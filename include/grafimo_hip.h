@@ -737,6 +737,47 @@ int gfm_graph_haplotype_class_records(int32_t n_regions, int32_t n_hap, const in
                                       const uint64_t *d_group_bits, int32_t n_groups, int32_t *d_count, int32_t *d_first,
                                       int32_t *d_group_counts, void *stream);
 
+/* ------------------------------------------------------------------ haplotype sequences: the bases a haplotype spells in a region
+ * THE RULE.  Haplotype h of a graph spells one sequence over the chromosome by walking the reference: at a position the
+ * substitution it carries replaces the base (its first carried ALT in slot order); the FIRST insertion in site order it carries at
+ * that anchor is read behind the anchor, later ones at that anchor are not; if no insertion was read there, the first deletion
+ * it carries at that anchor jumps over its span; every site anchored on a jumped-over base is ignored.  Every spelled base has
+ * a coordinate -- its own reference position (0-based), or its anchor's if it was inserted -- and an inserted flag.  The region
+ * sequence of h in [S, E) clipped to the chromosome is the contiguous stretch of spelled bases with coord + inserted >= S and
+ * coord < E: exactly the bases a report row of the region can contain (start in [S, E), stop <= E).  A base inserted behind
+ * S - 1 belongs, the anchor S - 1 itself does not; bases inserted behind E - 1 belong; an empty region gives an empty sequence;
+ * a region wholly under a carried deletion gives an empty sequence or inserted bases only.  Haplotype -1 is the reference: no
+ * ALT anywhere (it can be spelled on a graph without haplotypes).
+ *
+ * n_seqs (region, haplotype) pairs in device memory, d_seq_region / d_seq_hap int32 [n_seqs], over the n_regions host regions
+ * h_starts / h_stops (0-based, half-open, clipped here).  Count first, then fill:
+ *   d_bases NULL (measure only): d_len int32 [n_seqs] receives the number of bases of every pair, *h_total (host, optional)
+ *     their sum.  The caller makes the exclusive scan d_off int64 [n_seqs + 1] of the lengths and allocates.
+ *   d_bases uint8 [capacity]: the lengths are measured again (or, with GFM_SEQS_HAVE_LENGTHS, d_len is taken as an earlier
+ *     call left it for the same pairs), then the bases of pair n are written at d_off[n] ..; d_coord int32 [capacity]
+ *     (optional) receives per base its coordinate, ~coordinate for an inserted base; d_key uint64 [n_seqs] the content key of
+ *     every sequence: the sum mod 2^64 over its bases of mix64(seed, offset << 8 | base), offset counted from the sequence's
+ *     start, masked to key_bits (1 .. 64; below 64 a lab knob).  Equal sequences have equal keys; sequences of equal key are
+ *     compared with gfm_sequences_verify.  capacity and d_off count bases.
+ * Nothing is zeroed by the caller; every d_len and d_key entry is written.  GFM_ERR_INVALID: a haplotype >= the graph's number
+ * of haplotypes or < -1, a region index outside 0 .. n_regions - 1, h_stops[r] < h_starts[r], key_bits outside 1 .. 64, a
+ * graph without haplotypes when any haplotype >= 0 is asked for, a sequence of more than 2^31 - 1 bases -- the pairs are
+ * checked on the device and nothing is filled.  GFM_ERR_OVERFLOW: capacity < the total (nothing is written), or d_off is not
+ * the scan of the lengths inside capacity (the sequences that do not fit are left out; nothing is written out of bounds).
+ * The call WAITS for the stream (it reads the verdict of the check and the total); the handle's calls are serialised as
+ * gfm_graph_score's.  gfm_graph_profile_enable brackets the measure and the fill launch. */
+#define GFM_SEQS_HAVE_LENGTHS 1u
+int gfm_graph_haplotype_sequences(gfm_graph_t g, int32_t n_regions, const int64_t *h_starts, const int64_t *h_stops,
+                                  int64_t n_seqs, const int32_t *d_seq_region, const int32_t *d_seq_hap, int32_t *d_len,
+                                  const int64_t *d_off, int64_t capacity, uint8_t *d_bases, int32_t *d_coord, uint64_t seed,
+                                  int32_t key_bits, uint64_t *d_key, uint32_t flags, int64_t *h_total, void *stream);
+
+/* Graph-independent: n_seqs (< 2^31) sequences d_bases at d_off int64 [n_seqs + 1] (bases), d_same_as int32 [n_seqs] the
+ * sequence that sequence n is claimed to equal byte for byte, or n itself.  Length first, then the bytes: bit 0 of *d_status
+ * (cleared by the caller) is set on the first difference, or on a d_same_as outside 0 .. n_seqs - 1.  Enqueue only. */
+int gfm_sequences_verify(int64_t n_seqs, const int64_t *d_off, const uint8_t *d_bases, const int32_t *d_same_as,
+                         int32_t *d_status, void *stream);
+
 /* ------------------------------------------------------------------ hit pairs: rows close to each other that share carriers
  * Graph-independent (csrc/hit_pairs.hip).  n rows (n < 2^31 - 1) in device memory, in ascending (d_group, d_lo) order:
  * d_group int32, d_lo <= d_hi int64 (|x| < 2^61), d_masks uint64 [n][hw] (hw >= 1 words of a bitset whose unused tail
