@@ -25,6 +25,7 @@ GFM_NO_SELECT = 2**31 - 1
 GFM_FLAG_RESET_HITS = 1
 GFM_FLAG_CLEAR_HIST = 2
 GFM_FLAG_CALLER_ORDERS_REUSE = 4
+GFM_FLAG_OVERLAP_LAUNCHES = 8
 GFM_MAX_WIDTH = 64
 GFM_BEST_ROW_BITS = 44
 GFM_GRAPH_FORWARD_ONLY = 1
@@ -72,6 +73,8 @@ PROTOTYPES = {
                                 c_void_p, c_i64, c_void_p, ctypes.c_uint32, c_void_p, c_void_p]),
     "gfm_score_kmers_multi": (c_int, [c_void_p, c_int, c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_i64,
                                       c_void_p, c_void_p, c_void_p, ctypes.c_uint32, c_void_p]),
+    "gfm_overlapped_launches": (c_int, [c_void_p, P(c_u64)]),
+    "gfm_motif_set_overlap": (c_int, [c_void_p, c_int]),
     "gfm_score_kmers_multi_plan": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     "gfm_profile_enable": (c_int, [c_void_p, c_int, c_int]),
     "gfm_profile_read": (c_int, [c_void_p, c_void_p, c_int, P(c_int)]),

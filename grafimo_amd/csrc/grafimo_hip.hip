@@ -85,6 +85,21 @@ struct gfm_motif {
     hipStream_t last_st = nullptr, last_tail = nullptr;
     unsigned same_pair_run = 0;     // consecutive calls made with (last_st, last_tail) so far
     hipEvent_t ev_scored[kWorkspaces] = {};   // score kernel of the last call on a workspace done
+    // GFM_FLAG_OVERLAP_LAUNCHES: two streams of the handle's own (created on first use) that take the score kernels of
+    // flagged calls in turn, call_no & 1, so that consecutive kernels carry no barrier between them.  launch_last[i]
+    // is the completion event of the last kernel put on launch_st[i] and not yet joined by a call that went to the
+    // caller's stream (join_launch_streams); it is one of ev_scored[] / ev1[], which nothing records again before
+    // that join: the next users of those events are calls later than the joining one.
+    hipStream_t launch_st[2] = {};
+    hipEvent_t launch_last[2] = {};
+    // A flagged call that finds the caller's stream busy still goes to its launch stream, behind ev_join[] recorded on
+    // the caller's stream: ordered behind whatever that stream holds (a producer of the k-mers, or merely this
+    // pipeline's own earlier kernels), not behind the other launch stream.  `quiet`: such calls still to come that
+    // order themselves this way WITHOUT asking -- hipStreamQuery of a busy stream is not free (below).
+    hipEvent_t ev_join[kWorkspaces] = {};
+    unsigned quiet = 0;
+    bool overlap_on = true;         // gfm_motif_set_overlap: false = the flag is ignored
+    unsigned long long overlapped = 0;   // score kernels launched on a launch stream so far (gfm_overlapped_launches)
     hipEvent_t ev_posted[kWorkspaces] = {};   // its post kernel done (workspace free again)
     bool posted_valid[kWorkspaces] = {};
     // separate workspace of gfm_select_hits (runs on the caller's tail stream, next to scoring)
@@ -328,6 +343,64 @@ int launch_post(gfm_motif *m, const unsigned *partials, int hist_slabs, unsigned
     const PostJob q = post_job(m, partials, hist_slabs, d_hist, win_lo, win_nb, spill, resid, resid_n, hit_slabs, ctl,
                                ctl_slot, d_hit_rows, cap, d_hit_count);
     return launch_posts(&q, 1, st);
+}
+
+// Stream order between the caller's stream and the kernels of earlier GFM_FLAG_OVERLAP_LAUNCHES calls, which sit on the
+// handle's launch streams: `st` waits for the last of them.  Called by every score call that launches on `st`; a no-op
+// (two pointer tests) unless overlapped launches are outstanding, i.e. only where a pipeline changes mode.
+int join_launch_streams(gfm_motif *m, hipStream_t st)
+{
+    for (int i = 0; i < 2; ++i) {
+        if (!m->launch_last[i]) continue;
+        HIP_TRY(hipStreamWaitEvent(st, m->launch_last[i], 0));
+        m->launch_last[i] = nullptr;
+    }
+    return GFM_OK;
+}
+
+// The first launch on a new stream pays for the stream and its hardware queue: 14 ms between two score kernels in
+// the trace when that launch was the first overlapped score kernel, i.e. inside a pipeline's steady state
+// (profiles/score_overlap_ab.txt, section 1).  So the call just BEFORE the first one that may overlap -- the fourth of
+// a pipeline on the handle, still in its warm-up; a call that qualifies in every other respect -- creates the two
+// streams and puts an empty kernel on each.  Nothing waits for those.  Calls that can never overlap (a second user of
+// the handle in between, appending selections) create nothing.
+__global__ void launch_stream_warm_kernel() {}
+
+int ensure_launch_streams(gfm_motif *m)
+{
+    for (int i = 0; i < 2; ++i) {
+        if (m->launch_st[i]) continue;
+        HIP_TRY(hipStreamCreateWithFlags(&m->launch_st[i], hipStreamNonBlocking));
+        hipLaunchKernelGGL(launch_stream_warm_kernel, dim3(1), dim3(kWave), 0, m->launch_st[i]);
+        HIP_TRY(hipGetLastError());
+    }
+    for (int i = 0; i < kWorkspaces; ++i)
+        if (!m->ev_join[i]) HIP_TRY(hipEventCreateWithFlags(&m->ev_join[i], hipEventDisableTiming));
+    return GFM_OK;
+}
+
+// Whether nothing is pending on the caller's stream (whatever is could be the producer of the k-mers, which only that
+// stream orders): then a flagged call's kernel needs no wait at all.  Asking a BUSY stream costs: the runtime puts a
+// marker of its own into the stream to learn when it drains, and a pipeline that asked at every step while its own
+// kernels kept the stream busy ran 86.1 us a step against the parent's 79.1 on that box (0.612 against 0.568 ms at
+// 1.25e8 rows; profiles/score_overlap_ab.txt, section 4).  So after a "busy" the next three flagged calls do not ask and take the ordered way;
+// by then a pipeline that has moved to the launch streams has left the caller's stream empty.
+int caller_stream_idle(gfm_motif *m, hipStream_t st, bool *idle)
+{
+    *idle = false;
+    if (m->quiet) {
+        --m->quiet;
+        return GFM_OK;
+    }
+    const hipError_t q = hipStreamQuery(st);
+    if (q != hipSuccess) {
+        (void)hipGetLastError();     // hipErrorNotReady is an answer, not a failure of this call
+        if (q != hipErrorNotReady) HIP_TRY(q);
+        m->quiet = 3;
+        return GFM_OK;
+    }
+    *idle = true;
+    return GFM_OK;
 }
 
 void fill_motif_args(MotifArgs &a, gfm_motif *m, int ws, int slot, int use_hist, int win_lo, int win_nb,
@@ -792,6 +865,10 @@ GFM_API void gfm_motif_destroy(gfm_motif_t m)
     for (auto e : m->tev0) (void)hipEventDestroy(e);
     for (auto e : m->tev1) (void)hipEventDestroy(e);
     if (m->ev_selected) (void)hipEventDestroy(m->ev_selected);
+    for (int i = 0; i < 2; ++i)
+        if (m->launch_st[i]) (void)hipStreamDestroy(m->launch_st[i]);
+    for (int i = 0; i < kWorkspaces; ++i)
+        if (m->ev_join[i]) (void)hipEventDestroy(m->ev_join[i]);
     delete m;
 }
 
@@ -947,6 +1024,8 @@ GFM_API int gfm_score_kmers(gfm_motif_t m, const uint8_t *d_kmers, int64_t n, in
     if (n == 0) {
         if ((flags & GFM_FLAG_RESET_HITS) && d_hit_count) {
             if (split) {  // keep the tail stream ordered behind what the main stream holds
+                const int rcj = join_launch_streams(m, st);   // (ev_scored[0] may be what a launch stream's last kernel completes)
+                if (rcj) return rcj;
                 HIP_TRY(hipEventRecord(m->ev_scored[0], st));
                 HIP_TRY(hipStreamWaitEvent(tail, m->ev_scored[0], 0));
             }
@@ -990,12 +1069,6 @@ GFM_API int gfm_score_kmers(gfm_motif_t m, const uint8_t *d_kmers, int64_t n, in
             const long long cap = (nchunks + per_turn - 1) / per_turn * per_turn;
             if (best_cap < 0 || cap < best_cap) { best_cap = cap; nslabs = g; }
         }
-#ifdef GFM_LAB
-        if (const char *e = std::getenv("GRAFIMO_SCORE_GRID")) {   // force the grid size
-            const int g = atoi(e);
-            if (g >= 1 && g <= m->max_slabs) nslabs = g;
-        }
-#endif
     }
 
     const unsigned k = m->call_no++;
@@ -1006,9 +1079,45 @@ GFM_API int gfm_score_kmers(gfm_motif_t m, const uint8_t *d_kmers, int64_t n, in
     // hit list additionally needs the count published by call k-1.
     const bool same_owner = st == m->last_st && tail == m->last_tail;
     const bool caller_orders = (flags & GFM_FLAG_CALLER_ORDERS_REUSE) && same_owner && m->same_pair_run >= (unsigned)kWorkspaces;
+    // ... and this call is the last one before that holds (the next call of the same pair will be honoured)
+    const bool orders_next = (flags & GFM_FLAG_CALLER_ORDERS_REUSE) && same_owner && m->same_pair_run + 1 == (unsigned)kWorkspaces;
     m->same_pair_run = same_owner ? m->same_pair_run + 1 : 1;
     m->last_st = st;
     m->last_tail = tail;
+    // GFM_FLAG_OVERLAP_LAUNCHES: the kernel goes to launch stream k & 1 and nothing in front of it waits for the kernel
+    // of call k-1.  Only where the reuse promise holds (the workspace, the HitCtl slots and the caller's buffers of call
+    // k - kWorkspaces are free by the caller's word, not by stream order) and where the call does not append to a list
+    // whose count call k-1's tail publishes.  With the caller's stream drained nothing at all stands in front of the
+    // kernel (the steady state); otherwise it waits for what that stream holds now -- and for nothing else.
+    bool overlap = false, idle = false;
+    if ((flags & GFM_FLAG_OVERLAP_LAUNCHES) && split && m->overlap_on && !(select && !reset) &&
+        (caller_orders || orders_next)) {
+        int rco = ensure_launch_streams(m);    // (on the call BEFORE the first that may overlap: see there)
+        if (!rco && caller_orders) {
+            overlap = true;
+            rco = caller_stream_idle(m, st, &idle);
+        }
+        if (rco) return rco;
+    }
+    hipStream_t kst = overlap ? m->launch_st[k & 1u] : st;
+    if (overlap && !idle) {
+        HIP_TRY(hipEventRecord(m->ev_join[ws], st));
+        HIP_TRY(hipStreamWaitEvent(kst, m->ev_join[ws], 0));
+    }
+    // An overlapped launch takes every available CU: the slots its last turn leaves empty are no loss, the next kernel's
+    // workgroups start on them, while a workgroup fewer is a share of the rows that waits for a later turn (2e7 rows,
+    // one box, alternating: 233 workgroups 83.3-83.7 us a step, 252 79.7-79.9; profiles/score_overlap_ab.txt, section 2).
+    if (overlap && want > avail) nslabs = avail;
+#ifdef GFM_LAB
+    if (const char *e = std::getenv("GRAFIMO_SCORE_GRID")) {   // force the grid size
+        const int g = atoi(e);
+        if (want > avail && g >= 1 && g <= m->max_slabs) nslabs = g;
+    }
+#endif
+    if (!overlap) {   // back in stream order behind the kernels of earlier overlapped calls
+        const int rcj = join_launch_streams(m, st);
+        if (rcj) return rcj;
+    }
     if (m->posted_valid[ws] && !caller_orders)
         HIP_TRY(hipStreamWaitEvent(st, m->ev_posted[ws], 0));
     if (split && select && !reset && m->posted_valid[ws_prev])
@@ -1019,9 +1128,13 @@ GFM_API int gfm_score_kmers(gfm_motif_t m, const uint8_t *d_kmers, int64_t n, in
                     reinterpret_cast<long long *>(d_hit_rows), hit_capacity,
                     reset ? nullptr : reinterpret_cast<unsigned long long *>(d_hit_count));
     hipEvent_t scored = split ? m->ev_scored[ws] : nullptr;
-    int rc = dispatch_quad(m->W, 1, m, d_kmers, n, row_base, &args, m->lds_bytes, nslabs, m->q_waves, st, false,
+    int rc = dispatch_quad(m->W, 1, m, d_kmers, n, row_base, &args, m->lds_bytes, nslabs, m->q_waves, kst, false,
                            split ? &scored : nullptr);
     if (rc) return rc;
+    if (overlap) {
+        m->launch_last[k & 1u] = scored;
+        if (idle) ++m->overlapped;
+    }
     if (split) HIP_TRY(hipStreamWaitEvent(tail, scored, 0));
     m->tail_pending = -1;
     if (split && m->ev_last >= 0 && !m->tev0.empty()) {   // a timed call: the tail's clock starts when the score kernel is done
@@ -1116,6 +1229,7 @@ GFM_API int gfm_score_kmers_multi(const gfm_motif_t *motifs, int n_motifs, const
             const unsigned c = mo->call_no++;
             mo->same_pair_run = 0;             // another user of the handle: see gfm_motif::same_pair_run
             mo->last_st = mo->last_tail = nullptr;
+            if (const int rcj = join_launch_streams(mo, st)) return rcj;
             ws[k] = (int)(c % (unsigned)kWorkspaces);
             slot[k] = (int)(c % (unsigned)kCtlSlots);
             mo->posted_valid[ws[k]] = false;   // single stream: stream order protects the workspace
@@ -1178,11 +1292,33 @@ GFM_API int gfm_score_kmers_multi_plan(const gfm_motif_t *motifs, int n_motifs, 
     return GFM_OK;
 }
 
+GFM_API int gfm_motif_set_overlap(gfm_motif_t m, int enabled)
+{
+    if (!m) return fail(GFM_ERR_INVALID, "motif is NULL");
+    m->overlap_on = enabled != 0;
+    return GFM_OK;
+}
+
+GFM_API int gfm_overlapped_launches(gfm_motif_t m, uint64_t *count)
+{
+    if (!m || !count) return fail(GFM_ERR_INVALID, "NULL argument");
+    *count = m->overlapped;
+    return GFM_OK;
+}
+
 GFM_API int gfm_profile_enable(gfm_motif_t m, int slots, int every)
 {
     if (!m || slots < 0 || every < 1) return fail(GFM_ERR_INVALID, "bad argument");
     m->ev_every = every;
     m->ev_calls = 0;
+    // On a timed launch the timer's stop event is also what completes with the kernel (dispatch_quad), and
+    // launch_last[] may still name it for a later join_launch_streams: wait for those kernels here, on the host (this
+    // is a measurement aid, called between runs), so that no destroyed event is ever waited on.
+    for (int i = 0; i < 2; ++i) {
+        if (!m->launch_last[i]) continue;
+        HIP_TRY(hipEventSynchronize(m->launch_last[i]));
+        m->launch_last[i] = nullptr;
+    }
     for (auto e : m->ev0) (void)hipEventDestroy(e);
     for (auto e : m->ev1) (void)hipEventDestroy(e);
     for (auto e : m->tev0) (void)hipEventDestroy(e);

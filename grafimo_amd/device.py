@@ -4,6 +4,7 @@ Everything numeric is done by libgrafimo_hip.so; torch is used only for device
 buffers, streams and (in distributed.py) torch.distributed over RCCL.
 """
 import ctypes
+import os
 from collections import OrderedDict
 from typing import List, Optional
 
@@ -77,6 +78,11 @@ class DeviceMotif:
         lo, hi = ctypes.c_int32(), ctypes.c_int32()
         nv.check(nv.lib().gfm_motif_score_range(self._h, ctypes.byref(lo), ctypes.byref(hi)))
         self.score_lo, self.score_hi = lo.value, hi.value
+        # the switch of GFM_FLAG_OVERLAP_LAUNCHES that needs no rebuild, read HERE once per handle (the library reads no
+        # variable of its own for it: a C caller uses gfm_motif_set_overlap): GRAFIMO_SCORE_OVERLAP=0 makes the library
+        # ignore the flag on this handle whoever passes it (A/B runs, bisecting); scan.KmerScanner reads the same variable
+        if os.environ.get("GRAFIMO_SCORE_OVERLAP", "").strip() == "0":
+            self.set_overlap(False)
 
     @staticmethod
     def _numbers_of(motif, use_motif_pmf=True):
@@ -330,6 +336,16 @@ class DeviceMotif:
         n = ctypes.c_int(0)
         nv.check(nv.lib().gfm_profile_read(self._h, nv.ptr(ms), capacity, ctypes.byref(n)))
         return ms[: n.value].copy()
+
+    def set_overlap(self, enabled: bool):
+        """Whether this handle honours GFM_FLAG_OVERLAP_LAUNCHES (it does unless told otherwise)."""
+        nv.check(nv.lib().gfm_motif_set_overlap(self._h, int(bool(enabled))))
+
+    def overlapped_launches(self) -> int:
+        """Score kernels this handle launched on its own launch streams so far (GFM_FLAG_OVERLAP_LAUNCHES honoured)."""
+        n = ctypes.c_uint64(0)
+        nv.check(nv.lib().gfm_overlapped_launches(self._h, ctypes.byref(n)))
+        return int(n.value)
 
     def profile_mark_tail(self, stream=None):
         """gfm_profile_mark_tail: stop event of the tail of the last call if that call was a timed one."""

@@ -7,6 +7,7 @@ path is the all-reduce of the per-motif score histogram (BH ranks are global); h
 gathered to rank 0 for the report.  The collective + table work of one batch runs on a side
 stream so that it overlaps the score kernel of the next batch.
 """
+import os
 from typing import Optional
 
 import numpy as np
@@ -37,6 +38,27 @@ def score_ring_step(turn: int, n_slots: int, n_arrays: int, tail_reads):
     return array, None
 
 
+# GRAFIMO_SCORE_OVERLAP=0|1 overrides.  (device.DeviceMotif reads the same variable when it creates a handle and tells the
+# library to ignore the flag on that handle at 0: gfm_motif_set_overlap.  The library itself reads no variable for this.)
+OVERLAP_LAUNCHES_DEFAULT = True
+
+
+def overlap_launches(host_paced: bool, side_stream: bool, collective: bool, n_slots: int, env: Optional[str] = None) -> bool:
+    """Whether a KmerScanner passes GFM_FLAG_OVERLAP_LAUNCHES, as a pure function (no torch, no GPU).  The flag moves a
+    batch's score kernel off the caller's stream, next to the previous batch's, so everything that orders the batches
+    must not be stream order: the HOST paces slot and score-array reuse (host_paced), the outputs are consumed behind
+    the side stream (finish(), collect(), slot.done), and the library's workspace ring covers the slots
+    (n_slots <= GFM_WORKSPACE_RING, the condition of GFM_FLAG_CALLER_ORDERS_REUSE).  Off with a process group: RCCL
+    kernels then sit beside the grid, and how the two share the compute units has not been measured.
+    `env`: the value of GRAFIMO_SCORE_OVERLAP ("0" off, "1" on, anything else: OVERLAP_LAUNCHES_DEFAULT); it chooses
+    among the cases that qualify and never enables one that does not."""
+    if not (host_paced and side_stream) or collective or n_slots > _nv.GFM_WORKSPACE_RING:
+        return False
+    if env is not None and env.strip() in ("0", "1"):
+        return env.strip() == "1"
+    return OVERLAP_LAUNCHES_DEFAULT
+
+
 class ScanSlot:
     """One set of device buffers for a batch of up to n_rows k-mers."""
 
@@ -59,6 +81,7 @@ class ScanSlot:
         self.used = False
         self.reads_scores = False   # whether the tail of the slot's current batch reads its scores (KmerScanner.enqueue)
         self.gathered = None
+        self.kmers = None     # the batch's k-mer tensor while its score kernel may read it off the caller's stream (KmerScanner.enqueue)
         # raw addresses for the ctypes fast path
         self.p_scores = self.scores.data_ptr()
         self.p_hist = self.hist.data_ptr()
@@ -146,12 +169,29 @@ class KmerScanner:
         # scanner: the library honours the flag only while the ring's worth of calls before this one on the handle came from
         # the same stream pair, and orders the reuse itself when another scanner or a batched call was in between.)
         self._reuse_flag = _nv.GFM_FLAG_CALLER_ORDERS_REUSE if n_slots <= _nv.GFM_WORKSPACE_RING else 0
+        # ... and consecutive batches share nothing, so their score kernels may run side by side where one ramps down and
+        # the next ramps up (GFM_FLAG_OVERLAP_LAUNCHES: the library launches them on two streams of its own in turn).
+        # The k-mers of a batch must then be complete when enqueue() is called -- the library falls back to the caller's
+        # stream when that stream still holds work -- and a consumer of slot.scores goes through finish() / collect() /
+        # slot.done like a consumer of the hit list: the caller's stream no longer orders it behind the score kernel.
+        self.overlap = overlap_launches(self.host_paced, side_stream, self.collective, n_slots,
+                                        os.environ.get("GRAFIMO_SCORE_OVERLAP"))
+        if self.overlap:
+            self._reuse_flag |= _nv.GFM_FLAG_OVERLAP_LAUNCHES
         # q-value threshold: select from the p < t candidates the score kernel collects (enqueue) instead of
         # reading every score again; False = the separate pass over the scores (measurement aid)
         self.candidates = bool(candidates)
         # measurement aid (bench.py tail_ms): close the tail timing of a timed call (gfm_profile_mark_tail) behind the
         # last thing the step enqueues -- one more ctypes call per step, so only on request
         self.profile_tail = False
+        # Batches with a q-value threshold keep their score kernel on the caller's stream even where the scanner overlaps
+        # launches: their tail is the longest (q-table, then the selection among the candidates, each kernel waiting for a
+        # CU), and under overlap the next kernel's first workgroups sit on the CUs the grid leaves free for it.  Measured at
+        # W = 30, 1e8 rows (bench.py config 4, same box): 0.661 ms a step overlapped against the parent's 0.619, 0.633
+        # against 0.657 in stream order (profiles/score_overlap_ab.txt, sections 6 and 7) -- but 0.654 against 0.620 in stream
+        # order in the next pair of runs (section 8): twelve steps do not resolve 5 %, and overlap was never seen to gain
+        # there, so these batches stay as they were.  True: overlap them too (tests).
+        self.overlap_qvalue_batches = False
         self._turn = 0
         # entries of a slot's hit buffer ([count | hits...]) that a gather moves: the whole buffer until
         # size_gather() has seen how many hits a batch really holds
@@ -201,7 +241,13 @@ class KmerScanner:
         """Enqueue the whole path for one batch; returns the slot holding its outputs.
         With two slots nothing here synchronises with the host; with three or more (host_paced) the host
         waits for the batch n_slots back, which the device finished long ago unless the host runs more than
-        n_slots - 1 batches ahead.  Kept lean on purpose: a step is ~100 us of GPU
+        n_slots - 1 batches ahead.
+        With overlapped launches (self.overlap) the score kernel does not run on the caller's stream: `d_kmers` must be
+        COMPLETE when this is called (work still pending on the caller's stream is waited for, at the price of the overlap)
+        and must not be written until the batch is done (slot.done).  The scanner keeps the tensor referenced in the slot
+        until the slot's next batch, so a temporary may be passed: torch's allocator would otherwise hand its block to the
+        caller's next allocation, which only the caller's stream orders.  The batch's outputs, slot.scores included, are
+        ordered behind the SIDE stream: consume them through finish(), collect() or slot.done.  Kept lean on purpose: a step is ~100 us of GPU
         time, so the host side (ctypes calls with cached raw pointers, no torch dispatch unless a
         collective is needed) must stay well below that or the GPU starves."""
         if on_qvalue and not want_qvalues:      # the reference asserts this in ResultTmp.to_df
@@ -222,6 +268,9 @@ class KmerScanner:
             else:
                 main.wait_event(slot.done)
         slot.used = True
+        if self.overlap:
+            # (the slot's previous batch is done -- the host just waited for it -- so dropping ITS tensor here is safe)
+            slot.kmers = d_kmers
         if self._score_ring < n_slots:
             # a shorter score ring: this turn's array was written by younger batches than the slot's previous one.  The hazard is
             # an EARLIER writer's tail still reading the array (per-region best hit, selection on q: gfm_select_hits always,
@@ -241,9 +290,13 @@ class KmerScanner:
         n = int(d_kmers.shape[0])
         kp = d_kmers.data_ptr() if n else None
         h = dm.handle
-        # the score kernel goes to the main stream; the library puts its post kernel (histogram
-        # slabs -> slot.hist, residual hits -> slot.hits) on the tail stream behind an event
+        # the score kernel goes to the main stream -- or, with overlapped launches, to one of the library's two launch
+        # streams in turn; the library puts its post kernel (histogram slabs -> slot.hist, residual hits -> slot.hits)
+        # on the tail stream behind an event that completes with the score kernel
         use_cand = on_qvalue and self.candidates
+        reuse_flag = self._reuse_flag
+        if on_qvalue and not self.overlap_qvalue_batches:
+            reuse_flag &= ~_nv.GFM_FLAG_OVERLAP_LAUNCHES
         if not on_qvalue:
             key = float(threshold)
             cut = self._cutoffs.get(key)
@@ -251,10 +304,10 @@ class KmerScanner:
                 cut = self._cutoffs[key] = dm.pvalue_cutoff(key)
             _nv.check(lib.gfm_score_kmers(h, kp, n, slot.p_scores, slot.p_hist if want_qvalues else None,
                                           cut, int(row_base), slot.p_hit_rows, slot.hit_capacity,
-                                          slot.p_hit_count, _nv.GFM_FLAG_RESET_HITS | self._reuse_flag, main_p, tail_p))
+                                          slot.p_hit_count, _nv.GFM_FLAG_RESET_HITS | reuse_flag, main_p, tail_p))
         elif not use_cand:
             _nv.check(lib.gfm_score_kmers(h, kp, n, slot.p_scores, slot.p_hist, _nv.GFM_NO_SELECT, 0,
-                                          None, 0, None, self._reuse_flag, main_p, tail_p))
+                                          None, 0, None, reuse_flag, main_p, tail_p))
         else:
             # q-value threshold: the cutoff needs the global histogram, but q >= p, so the rows with q < t are
             # among those with p < t -- the score kernel collects THOSE on the fly (candidates), and the
@@ -268,7 +321,7 @@ class KmerScanner:
             slot.candidates()
             _nv.check(lib.gfm_score_kmers(h, kp, n, slot.p_scores, slot.p_hist, cut, int(row_base),
                                           slot.p_cand_rows, slot.hit_capacity, slot.p_cand_count,
-                                          _nv.GFM_FLAG_RESET_HITS | self._reuse_flag, main_p, tail_p))
+                                          _nv.GFM_FLAG_RESET_HITS | reuse_flag, main_p, tail_p))
         if want_qvalues:
             if self.collective:
                 with torch.cuda.stream(tail):

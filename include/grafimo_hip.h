@@ -54,6 +54,30 @@ extern "C" {
  * scanner, a batched call) makes it fall back to its own event wait. */
 #define GFM_FLAG_CALLER_ORDERS_REUSE 4u
 #define GFM_WORKSPACE_RING 4
+/* gfm_score_kmers with a tail stream, together with GFM_FLAG_CALLER_ORDERS_REUSE: consecutive calls have no data
+ * dependency on each other, so their score kernels need not run in stream order.  The library then launches the kernel
+ * on one of two streams of the handle's own, taken in turn, instead of on `stream`: no barrier stands between the
+ * kernels of calls k and k+1, the workgroups of k+1 take the compute units as those of k leave them, and the ramp-down
+ * of one kernel overlaps the ramp-up of the next.  What a flagged call promises and gets:
+ *   - the k-mers are COMPLETE when the call is made, and stay untouched until the call's tail work is done: the kernel
+ *     is not ordered behind `stream`.  The library checks the cheap half of that: when hipStreamQuery(stream) finds
+ *     anything pending on `stream` (possibly the k-mers' producer) this call's kernel -- and, unasked, those of the next
+ *     three flagged calls -- waits for an event recorded on `stream` at the call: ordered behind all that `stream` holds
+ *     then, still not behind the previous call's kernel.  An event wait appears nowhere else;
+ *   - d_scores, d_hist and d_hit_* are ordered behind `tail_stream` at this point, and NOT behind `stream`: a consumer
+ *     waits for the tail stream (an event recorded on it after the call), also for the scores;
+ *   - the promise of GFM_FLAG_CALLER_ORDERS_REUSE extends to d_scores and d_kmers: whoever read or wrote them before
+ *     is done when the call is made.
+ * Honoured only where GFM_FLAG_CALLER_ORDERS_REUSE is (the GFM_WORKSPACE_RING calls before this one on the handle came
+ * from the same stream pair), and not for a call that appends to a hit list (selection without GFM_FLAG_RESET_HITS:
+ * its kernel reads the count the previous call's tail publishes).  Whether to pass it is the caller's choice per
+ * call: under overlap the next kernel's first workgroups take the compute units a split call leaves free for the tail,
+ * so a long tail (a q-value threshold: q-table, then the selection) finishes later (scan.KmerScanner does not pass the
+ * flag for such batches).  gfm_motif_set_overlap(m, 0) makes a handle ignore
+ * the flag (A/B runs, bisecting: the Python binding calls it for every handle it creates while the environment
+ * variable GRAFIMO_SCORE_OVERLAP is 0).  gfm_score_kmers_multi, the streamed scan and the graph calls never overlap
+ * their launches. */
+#define GFM_FLAG_OVERLAP_LAUNCHES 8u
 /* a hit-list entry packs the global row id and the row's scaled score:
  * entry = (row << GFM_HIT_SCORE_BITS) | score   (score <= 1000*64 < 2^20) */
 #define GFM_HIT_SCORE_BITS 20
@@ -163,6 +187,14 @@ int gfm_score_kmers_multi(const gfm_motif_t *motifs, int n_motifs, const uint8_t
                           const int32_t *select_cutoffs, int64_t row_base,
                           int64_t *const *d_hit_rows, const int64_t *hit_capacity,
                           uint64_t *const *d_hit_count, uint32_t flags, void *stream);
+
+/* Number of score kernels this handle has launched on its own launch streams with nothing in front of them so far
+ * (GFM_FLAG_OVERLAP_LAUNCHES honoured, `stream` found empty); a flagged call that stayed on `stream` or waited for it
+ * does not count. */
+int gfm_overlapped_launches(gfm_motif_t m, uint64_t *count);
+/* enabled == 0: this handle ignores GFM_FLAG_OVERLAP_LAUNCHES from now on (its launches stay on the caller's stream);
+ * != 0: it honours the flag again (the default). */
+int gfm_motif_set_overlap(gfm_motif_t m, int enabled);
 
 /* How gfm_score_kmers_multi would group these motifs (no device work): group_size_out[i] = number of motifs of the
  * launch motif i rides in (1..3), waves_out[i] = waves per workgroup of that launch (16 or 8).  with_hist[i] != 0
