@@ -112,7 +112,7 @@ def get_parser():
                         "haplotype's total binding affinity -- the sum of 2^(log-odds / T) over every k-mer of its own "
                         "sequence --, beside the reference's (graph routes only)")
     p.add_argument("--affinity-temperature", dest="affinity_temperature", type=float, default=None, metavar="T",
-                   help="with --haplotype-affinity, --variant-affinity or --haplotype-classes: the temperature T > 0 the log-odds scores are "
+                   help="with --haplotype-affinity, --variant-affinity, --haplotype-classes or --query-variants: the temperature T > 0 the log-odds scores are "
                         "divided by; default 1")
     p.add_argument("--variant-affinity", action="store_true", dest="variant_affinity",
                    help="also write grafimo_variant_affinity[_MOTIF].tsv (printed with -f): per variant, the log2 of the mean "
@@ -124,7 +124,7 @@ def get_parser():
                    help="also write grafimo_hit_alleles[_MOTIF].tsv (printed with -f): the report's rows, each with the variant "
                         "alleles that make its k-mer and, with --haplotype-groups, its carriers per group (graph routes only)")
     p.add_argument("--haplotype-groups", dest="haplotype_groups", metavar="FILE",
-                   help="with --hit-alleles, --hit-pairs, --haplotype-classes or --haplotype-sequences: SAMPLE GROUP lines (the 1000 Genomes panel file reads as is), one "
+                   help="with --hit-alleles, --hit-pairs, --haplotype-classes, --haplotype-sequences or --query-variants: SAMPLE GROUP lines (the 1000 Genomes panel file reads as is), one "
                         "haplotypes_GROUP column per group")
     p.add_argument("--haplotype-classes", action="store_true", dest="haplotype_classes",
                    help="also write grafimo_haplotype_classes[_MOTIF].tsv (printed with -f) and "
@@ -138,6 +138,15 @@ def get_parser():
                         "printed with -f): per region the distinct sequences the haplotypes spell in it, each with its count, "
                         "its counts per --haplotype-groups group, the haplotype classes that spell it and its bases "
                         "(graph routes only)")
+    p.add_argument("--query-variants", dest="query_variants", metavar="FILE",
+                   help="also write grafimo_query_variants[_MOTIF].tsv and grafimo_query_variant_contexts[_MOTIF].tsv (printed "
+                        "with -f): the variants of the VCF FILE, which need not be in the panel, applied to every sequence "
+                        "background the haplotypes spell around them -- per background the best hit and the total affinity "
+                        "(--affinity-temperature) before and after, gain / loss on p < -t, and its haplotypes, also per "
+                        "--haplotype-groups group (graph routes only)")
+    p.add_argument("--query-all", action="store_true", dest="query_all",
+                   help="with --query-variants: keep every variant, not only those that create or destroy a hit on some "
+                        "background")
     p.add_argument("--hit-pairs", action="store_true", dest="hit_pairs",
                    help="also write grafimo_hit_pairs.tsv (printed with -f): the pairs of report rows -- of one motif or of "
                         "two -- of a region that lie within --pair-gap of each other and share carrier haplotypes, with how "
@@ -215,7 +224,8 @@ _GRAPH_TABLES = {"variant_effects": ("--variant-effects", "alleles"), "haplotype
                  "variant_affinity": ("--variant-affinity", "walks"), "hit_alleles": ("--hit-alleles", "walks"),
                  "hit_pairs": ("--hit-pairs", "walks"), "hit_linkage": ("--hit-linkage", "walks"),
                  "haplotype_classes": ("--haplotype-classes", "haplotypes"),
-                 "haplotype_sequences": ("--haplotype-sequences", "haplotypes")}
+                 "haplotype_sequences": ("--haplotype-sequences", "haplotypes"),
+                 "query_variants": ("--query-variants", "haplotypes")}
 
 
 def _graph_only(a, table):
@@ -253,7 +263,8 @@ def main(argv=None):
                  "threshold (drop --qvalueT)")
     _graph_only(a, "haplotype_hits")
     _graph_only(a, "haplotype_scores")
-    if a.affinity_temperature is not None and not (a.haplotype_affinity or a.variant_affinity or a.haplotype_classes):
+    if a.affinity_temperature is not None and not (a.haplotype_affinity or a.variant_affinity or a.haplotype_classes
+                                                    or a.query_variants):
         sys.exit("ERROR: --affinity-temperature goes with --haplotype-affinity or --variant-affinity or --haplotype-classes")
     if a.affinity_temperature is not None and not a.affinity_temperature > 0:
         sys.exit(f"ERROR: --affinity-temperature {a.affinity_temperature} is not > 0")
@@ -263,7 +274,8 @@ def main(argv=None):
     if a.variant_affinity_delta is not None and not a.variant_affinity_delta >= 0:
         sys.exit(f"ERROR: --variant-affinity-delta {a.variant_affinity_delta} is not >= 0")
     _graph_only(a, "variant_affinity")
-    if a.haplotype_groups and not (a.hit_alleles or a.hit_pairs or a.haplotype_classes or a.haplotype_sequences):
+    if a.haplotype_groups and not (a.hit_alleles or a.hit_pairs or a.haplotype_classes or a.haplotype_sequences
+                                   or a.query_variants):
         sys.exit("ERROR: --haplotype-groups goes with --hit-alleles or --hit-pairs or --haplotype-classes or "
                  "--haplotype-sequences")
     if a.class_min_haplotypes is not None and not a.haplotype_classes:
@@ -272,6 +284,13 @@ def main(argv=None):
         sys.exit(f"ERROR: --class-min-haplotypes {a.class_min_haplotypes} < 1")
     _graph_only(a, "haplotype_classes")
     _graph_only(a, "haplotype_sequences")
+    if a.query_all and not a.query_variants:
+        sys.exit("ERROR: --query-all goes with --query-variants")
+    if a.query_variants:
+        import os
+        if not os.path.isfile(a.query_variants):
+            sys.exit(f"ERROR: Unable to locate {a.query_variants}")
+    _graph_only(a, "query_variants")
     if a.pair_gap is not None and not a.hit_pairs:
         sys.exit("ERROR: --pair-gap goes with --hit-pairs")
     if a.pair_gap is not None and a.pair_gap[0] > a.pair_gap[1]:
@@ -439,6 +458,28 @@ def main(argv=None):
             fasta, tsv = haplotype_sequence_paths(wf)
             print(f"{len(hs)} haplotype sequences written to {write_haplotype_sequences_fasta(hs, fasta)}")
             print(f"{len(hs)} haplotype sequence versions written to {write_haplotype_sequence_versions(hs, tsv)}")
+    if a.query_variants:
+        from .query_variants import (MAX_ALLELE, compute_query_variants_many, normalise, print_query_variants, read_query_vcf,
+                                     write_query_variant_contexts, write_query_variants)
+        graph, regions, first_index = source("query_variants")
+        variants, too_long = [], 0
+        for v in read_query_vcf(a.query_variants):
+            _, nref, nalt = normalise(v[1], v[3], v[4])
+            if max(len(nref), len(nalt)) > MAX_ALLELE or not (nref or nalt):
+                too_long += 1
+                continue
+            variants.append(v)
+        if too_long:
+            print(f"WARNING: {too_long} query variants with an allele of more than {MAX_ALLELE} bases after trimming, or with "
+                  "REF equal to ALT, were skipped", file=sys.stderr)
+        tables = compute_query_variants_many(motifs, graph, variants, a.debug, wf, haplotype_groups=groups(first_index),
+                                             temperature=1.0 if a.affinity_temperature is None else a.affinity_temperature,
+                                             all_variants=a.query_all, skip_unusable=True)
+        emit(tables, write_query_variants, print_query_variants, lambda t: f"{len(t)} query variant rows")
+        if not a.text_only:
+            for motif, t in zip(motifs, tables):
+                print(f"{len(t.contexts_frame())} query variant context rows written to "
+                      f"{write_query_variant_contexts(t, motif, len(motifs), wf)}")
     if sequences_loc:
         import shutil
         shutil.rmtree(sequences_loc, ignore_errors=True)

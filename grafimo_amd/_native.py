@@ -38,6 +38,8 @@ GFM_VARIANT_KEEP_ZERO_FREQ = 2
 GFM_PAIRS_HAVE_OFFSETS = 1
 GFM_LINKAGE_HAVE_OFFSETS = 1
 GFM_SEQS_HAVE_LENGTHS = 1
+GFM_QUERY_MAX_ALLELE = 64
+GFM_EDIT_APPLIED, GFM_EDIT_ABSENT, GFM_EDIT_MISMATCH, GFM_EDIT_INVALID = 0, 1, 2, 3
 ABI_VERSION = 12
 RANGE = 1000
 
@@ -158,6 +160,9 @@ PROTOTYPES = {
     "gfm_graph_haplotype_sequences": (c_int, [c_void_p, c_i32, c_void_p, c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_void_p, c_i64,
                                               c_void_p, c_void_p, ctypes.c_uint64, c_i32, c_void_p, ctypes.c_uint32, P(c_i64), c_void_p]),
     "gfm_sequences_verify": (c_int, [c_i64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "gfm_graph_query_edits": (c_int, [c_void_p, c_i32, c_void_p, c_u64, c_i32, c_void_p, c_void_p, c_void_p, c_i32, c_void_p, c_void_p,
+                                      c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_void_p, ctypes.c_uint32, c_void_p, c_void_p,
+                                      c_void_p]),
     "gfm_hit_pairs": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_i32, c_i64, c_i64, c_i32, c_void_p, c_void_p, c_i64,
                               c_void_p, c_void_p, c_void_p, ctypes.c_uint32, P(c_i64), c_void_p]),
     "gfm_hit_linkage": (c_int, [c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_i64, c_i32, c_i32, c_i64,

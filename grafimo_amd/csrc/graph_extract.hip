@@ -2558,3 +2558,4 @@ inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 #include "gfm_graph_variant_affinity.hpp"
 #include "gfm_graph_hapclasses.hpp"
 #include "gfm_graph_hapsequences.hpp"
+#include "gfm_graph_query_variants.hpp"

@@ -810,6 +810,55 @@ int gfm_graph_haplotype_sequences(gfm_graph_t g, int32_t n_regions, const int64_
 int gfm_sequences_verify(int64_t n_seqs, const int64_t *d_off, const uint8_t *d_bases, const int32_t *d_same_as,
                          int32_t *d_status, void *stream);
 
+/* ------------------------------------------------------------------ query variants: an edit applied to a spelled sequence
+ * Graph-independent.  THE RULE.  A sequence x (gfm_graph_haplotype_sequences' d_bases) has per base a coordinate, ~coordinate
+ * for an inserted base (its d_coord).  An edit is (pos0, ref of lr bases, alt of la bases): a variant with the bases REF and
+ * ALT share at their start, then at their end, stripped; pos0 the 0-based position of the first remaining REF base; lr and la
+ * at most GFM_QUERY_MAX_ALLELE, not both 0.
+ *   lr > 0:  o = the offset in x of the non-inserted base with coordinate pos0.  GFM_EDIT_ABSENT unless every coordinate
+ *     pos0 .. pos0 + lr - 1 is carried by a non-inserted base of x (the background deletes one); GFM_EDIT_APPLIED when
+ *     x[o .. o + lr) are those bases in order, no inserted base between them, and equal ref compared without case; else
+ *     GFM_EDIT_MISMATCH (the background carries another allele there).
+ *   lr == 0 (a pure insertion between pos0 - 1 and pos0): o as above; ABSENT unless a non-inserted base carries pos0 - 1 too
+ *     (pos0 == 0: always ABSENT); APPLIED when that base is x[o - 1], else MISMATCH (inserted bases lie between).  When no base
+ *     carries pos0: APPLIED at o = len(x) if the LAST base of x is the non-inserted base pos0 - 1, MISMATCH at o = len(x) if it
+ *     is a base inserted behind pos0 - 1, else ABSENT -- x is taken to run to the end of its chromosome then, which the caller
+ *     knows and this entry does not (grafimo_amd.query_variants turns both into ABSENT when pos0 is not the chromosome's length).
+ *   The edited sequence is y = x[:o] + alt + x[o + lr:].  REF side: the window starts s of x with s <= o + lr - 1 and
+ *   s + W - 1 >= o (lr == 0: the windows across the junction), clipped to 0 <= s <= len(x) - W; ALT side: the same in y with la.
+ *   A side may have no window.  Every window is scored once per strand (GFM_GRAPH_FORWARD_ONLY: the forward strand only); a
+ *   k-mer holding a base that is not A, C, G, T scores min_val.  Per side: the best window by (score descending, s ascending,
+ *   '+' before '-') and the sum over its windows and strands of w[score], exact in uint64 whatever the order of the adds.
+ *
+ * n_motifs motifs of ONE width on the current device, d_weights[m] uint64 [table length] per motif and max_weight, the largest
+ * weight of all tables (host): refused when max_weight * 2 * (W + 64) passes 2^64 - 1.  The sequences: d_seq_offsets int64
+ * [n_seqs + 1], d_bases uint8, d_coord int32.  The edits: d_pos0 int64 [n_edits], d_ref_off / d_alt_off int32 [n_edits + 1]
+ * into d_ref_bytes / d_alt_bytes.  The items: d_item_seq / d_item_edit int32 [n_items].  d_records[m] receives one record per
+ * item: status, o (-1: no base carries pos0) and, when APPLIED, per side the key -- 0: no window, else
+ * (score + 1) << 8 | (64 - (s - o)) << 1 | (strand is '+') -- and the sum; keys and sums are 0 otherwise.  Every record is
+ * written.  d_status int32: a device word of the caller's, cleared and read here.
+ * n_items == 0 returns GFM_OK and touches nothing.  GFM_ERR_INVALID: a NULL pointer, motifs of different widths or on another
+ * device than the current one, an unknown flag; and, CHECKED ON THE DEVICE per item (its record's status is GFM_EDIT_INVALID,
+ * nothing is read through it): an item index outside its array, an edit with lr or la above 64 or both 0, sequence offsets
+ * that descend.  What the offsets point INTO is the caller's contract: d_seq_offsets within d_bases / d_coord, the edit
+ * offsets within their bytes.  The call WAITS for the stream (it reads the verdict of the check). */
+#define GFM_QUERY_MAX_ALLELE 64
+#define GFM_EDIT_APPLIED 0
+#define GFM_EDIT_ABSENT 1
+#define GFM_EDIT_MISMATCH 2
+#define GFM_EDIT_INVALID 3
+typedef struct {
+    int32_t status, o;
+    uint32_t ref_key, alt_key;
+    uint64_t ref_sum, alt_sum;
+} gfm_edit_record_t;
+int gfm_graph_query_edits(const gfm_motif_t *motifs, int32_t n_motifs, const uint64_t *const *d_weights, uint64_t max_weight,
+                          int32_t n_seqs, const int64_t *d_seq_offsets, const uint8_t *d_bases, const int32_t *d_coord,
+                          int32_t n_edits, const int64_t *d_pos0, const int32_t *d_ref_off, const uint8_t *d_ref_bytes,
+                          const int32_t *d_alt_off, const uint8_t *d_alt_bytes, int64_t n_items, const int32_t *d_item_seq,
+                          const int32_t *d_item_edit, uint32_t flags, gfm_edit_record_t *const *d_records, int32_t *d_status,
+                          void *stream);
+
 /* ------------------------------------------------------------------ hit pairs: rows close to each other that share carriers
  * Graph-independent (csrc/hit_pairs.hip).  n rows (n < 2^31 - 1) in device memory, in ascending (d_group, d_lo) order:
  * d_group int32, d_lo <= d_hi int64 (|x| < 2^61), d_masks uint64 [n][hw] (hw >= 1 words of a bitset whose unused tail
