@@ -1,0 +1,232 @@
+// gfm_graph_mutation_scan.hpp -- mutation scan: every single-base change at every offset of a spelled sequence, every window
+// the change touches scored before and after on both strands (included at the end of graph_extract.hip behind
+// gfm_graph_query_variants.hpp; it uses base_code, gfm_motif_view_, GX_TRY, gfail and align256).  Where query_edits_kernel
+// scores the 2 W windows of ONE edit with W lookups each, this kernel scores every window of a sequence ONCE and derives the
+// windows of all 4 n changes from the stored sums: an ALT window differs from its REF window in one table entry.
+//
+// THE RULE (include/grafimo_hip.h states it for the library; tests/mutation_scan_bruteforce.py on the host).  For a sequence x of
+// n bases and a motif of width W, for every offset o in 0 .. n - 1 and every base b in A, C, G, T:
+//   y = x with y[o] = b.  REF side: the window starts s of x with max(0, o - W + 1) <= s <= min(o, n - W).  ALT side: the same
+//   starts in y.  Every window is scored once per strand, or + only under GFM_GRAPH_FORWARD_ONLY.  A window that holds a base
+//   that is not A/C/G/T scores min_val on both strands; case is folded, as base_code does.  Per side: the best window by (score
+//   descending, s ascending, + before -), as the key ((score + 1) << 8) | ((64 - (s - o)) << 1) | plus, s - o in -(W - 1) .. 0,
+//   key 0: the side has no window (n < W); and the exact uint64 sum of w[score] over the side's windows and strands.  b equal
+//   to the folded x[o] gives ALT equal to REF; an x[o] that is no base has an all-min_val REF side, and each b can repair it.
+//
+// Work decomposition: the unit is a (sequence, tile of GFM_MUTSCAN_TILE offsets) pair, listed by the entry in a tile table
+// (scratch of the call) and checked on the device before anything is read through it; grid.y = motif, a workgroup strides
+// over the tiles.  Per workgroup the motif's packed two-strand table (W x 8 words) is staged once in LDS.  Per tile:
+//   phase 1  the base codes of the tile and a halo of W - 1 on each side go to LDS (a position outside the sequence is no
+//            base); every window start under them -- at most TILE + W - 1 -- is scored ONCE: the packed two-strand sum (W LDS
+//            lookups), the count of its non-base positions and, for the windows inside the sequence, the REF weight
+//            w[+ score] + w[- score] (the only weight loads a REF side costs) are kept in LDS;
+//   phase 2  a thread per offset o walks the at most W starts s = o - j (the lanes read consecutive LDS words: no bank
+//            conflict): the REF score is the stored sum, or min_val; the ALT score for b is sum - ftab[j][x[o]] + ftab[j][b]
+//            -- the halves of the packed word cannot borrow: each half of the sum contains the entry that is removed --; the
+//            window is valid when its non-base count minus (x[o] is no base) is 0.  The column of b == x[o] is the REF column
+//            and is copied, not loaded again.  Key maximum and uint64 sum per column in registers, w[score] through the cache;
+//            the five keys and five sums of o are written with plain stores.  No atomics but the status word's.
+// The tile is ONE wavefront's worth of offsets (64): a workgroup is a wavefront, its barriers cost nothing, no wavefront waits
+// for the halo pass of another, and a sequence wastes half a tile of lanes at its end, 32 offsets, whatever its length.
+// LDS: 2 048 (table) + 192 (codes) + 128 x (4 + 1 + 8) (sums, counts, REF weights) = 3 904 bytes a workgroup: 32 workgroups
+// a CU hold 122 KiB of its 160 -- the wavefront slots, not the LDS, bound the occupancy.
+namespace {
+
+constexpr int kMsTile = GFM_MUTSCAN_TILE, kMsThreads = kMsTile;
+constexpr int kMsHalo = GFM_MAX_WIDTH - 1;
+constexpr int kMsCodes = (kMsTile + 2 * kMsHalo + 15) & ~15;                        // 192
+constexpr int kMsWindows = (kMsTile + kMsHalo + 15) & ~15;                          // 128
+constexpr int kMsMotifs = 16;                                                        // motifs of one launch (grid.y)
+constexpr int kMsMaxBlocks = 1 << 16;
+constexpr int kMsBadTile = 1;
+
+struct MsTile {
+    long long begin;              // the sequence's first base in d_bases (and its first row in the results)
+    int len, start;               // its length; the tile's first offset
+};
+
+struct MsMotifs {
+    const unsigned *ftab[kMsMotifs];
+    const unsigned long long *wtab[kMsMotifs];
+    unsigned *keys[kMsMotifs];
+    unsigned long long *sums[kMsMotifs];
+    int min_val[kMsMotifs];
+};
+
+__global__ void __launch_bounds__(kMsThreads)
+mutation_scan_kernel(const MsTile *__restrict__ tiles, long long n_tiles, const uint8_t *__restrict__ bases, long long n_bases,
+                     MsMotifs mt, int W, int forward_only, int *__restrict__ status)
+{
+    __shared__ unsigned ftab_s[GFM_MAX_WIDTH * 8];
+    __shared__ unsigned long long wref_s[kMsWindows];
+    __shared__ unsigned wsum_s[kMsWindows];
+    __shared__ unsigned char code_s[kMsCodes], bad_s[kMsWindows];
+    const int m = blockIdx.y, tid = threadIdx.x;
+    for (int i = tid; i < W * 8; i += kMsThreads) ftab_s[i] = mt.ftab[m][i];
+    const unsigned long long *__restrict__ wtab = mt.wtab[m];
+    unsigned *__restrict__ keys = mt.keys[m];
+    unsigned long long *__restrict__ sums = mt.sums[m];
+    const unsigned min_val = (unsigned)mt.min_val[m];
+    const int halo = W - 1;
+    for (long long t = blockIdx.x; t < n_tiles; t += gridDim.x) {
+        const MsTile tile = tiles[t];
+        // ---- the tile, checked: everything read and written below lies inside its sequence (uniform: no thread stays behind)
+        if (tile.begin < 0 || tile.len <= 0 || tile.begin > n_bases - tile.len || tile.start < 0 || tile.start >= tile.len) {
+            if (tid == 0) atomicOr(status, kMsBadTile);
+            continue;
+        }
+        const uint8_t *__restrict__ x = bases + tile.begin;
+        const int len = tile.len, lo = tile.start, nt = min(kMsTile, len - lo);
+        const int c0 = lo - halo;                                 // code_s[i] is x[c0 + i]; window k starts at c0 + k
+        __syncthreads();                                          // (the table is staged; the last tile's windows are read)
+        for (int i = tid; i < nt + 2 * halo; i += kMsThreads) {
+            const int p = c0 + i;
+            code_s[i] = (unsigned char)((p >= 0 && p < len) ? base_code(x[p]) : 4u);
+        }
+        __syncthreads();
+        // ---- phase 1: every window start under the tile and its halo, once
+        for (int k = tid; k < nt + halo; k += kMsThreads) {
+            unsigned acc = 0u, nb = 0u;
+            for (int j = 0; j < W; ++j) {
+                const unsigned c = code_s[k + j];
+                acc += ftab_s[j * 8 + c];
+                nb += c >> 2;
+            }
+            const int s = c0 + k;
+            unsigned long long wr = 0ull;
+            if (s >= 0 && s <= len - W) {
+                wr = wtab[nb ? min_val : (acc & 0xffffu)];
+                if (!forward_only) wr += wtab[nb ? min_val : (acc >> 16)];
+            }
+            wsum_s[k] = acc;
+            bad_s[k] = (unsigned char)nb;
+            wref_s[k] = wr;
+        }
+        __syncthreads();
+        // ---- phase 2: a thread per offset; the starts s = o - j of the sequence's windows over o
+        if (tid < nt) {
+            const int o = lo + tid;
+            const unsigned xo = code_s[tid + halo], xbad = xo >> 2;
+            unsigned key_r = 0u, key_b[4] = {0u, 0u, 0u, 0u};
+            unsigned long long sum_r = 0ull, sum_b[4] = {0ull, 0ull, 0ull, 0ull};
+            const int j_lo = max(0, o - (len - W)), j_hi = min(halo, o);
+            for (int j = j_lo; j <= j_hi; ++j) {
+                const int k = tid + halo - j;
+                const unsigned acc = wsum_s[k], nb = bad_s[k];
+                const unsigned place = (unsigned)(64 + j) << 1;   // 64 - (s - o): an earlier start is larger
+                const unsigned rf = nb ? min_val : (acc & 0xffffu);
+                key_r = max(key_r, ((rf + 1u) << 8) | place | 1u);
+                if (!forward_only) key_r = max(key_r, (((nb ? min_val : (acc >> 16)) + 1u) << 8) | place);
+                sum_r += wref_s[k];
+                const bool valid = nb == xbad;                    // (no base of the window but x[o] itself is none)
+                const unsigned rest = acc - ftab_s[j * 8 + xo];
+#pragma unroll
+                for (unsigned b = 0; b < 4; ++b) {
+                    if (b == xo) continue;                        // the REF column: copied below
+                    const unsigned v = rest + ftab_s[j * 8 + b];
+                    const unsigned sf = valid ? (v & 0xffffu) : min_val;
+                    key_b[b] = max(key_b[b], ((sf + 1u) << 8) | place | 1u);
+                    sum_b[b] += wtab[sf];
+                    if (!forward_only) {
+                        const unsigned sr = valid ? (v >> 16) : min_val;
+                        key_b[b] = max(key_b[b], ((sr + 1u) << 8) | place);
+                        sum_b[b] += wtab[sr];
+                    }
+                }
+            }
+#pragma unroll
+            for (unsigned b = 0; b < 4; ++b)
+                if (b == xo) { key_b[b] = key_r; sum_b[b] = sum_r; }
+            // the columns REF, A, C, G, T; the codes are A 0, C 1, T 2, G 3
+            unsigned *kq = keys + (tile.begin + o) * 5;
+            unsigned long long *sq = sums + (tile.begin + o) * 5;
+            kq[0] = key_r; kq[1] = key_b[0]; kq[2] = key_b[1]; kq[3] = key_b[3]; kq[4] = key_b[2];
+            sq[0] = sum_r; sq[1] = sum_b[0]; sq[2] = sum_b[1]; sq[3] = sum_b[3]; sq[4] = sum_b[2];
+        }
+    }
+}
+
+}  // namespace
+
+GFM_API int gfm_sequence_mutation_scan(const gfm_motif_t *motifs, int32_t n_motifs, const uint64_t *const *d_weights,
+                                       uint64_t max_weight, int32_t n_seqs, const int64_t *seq_offsets, const uint8_t *d_bases,
+                                       uint32_t flags, uint32_t *const *d_keys, uint64_t *const *d_sums, int32_t *d_status,
+                                       void *stream)
+{
+    if (n_motifs < 1 || n_seqs < 0) return gfail(GFM_ERR_INVALID, "bad argument");
+    if (flags & ~(uint32_t)GFM_GRAPH_FORWARD_ONLY) return gfail(GFM_ERR_INVALID, "unknown flag");
+    if (n_seqs == 0) return GFM_OK;
+    if (!seq_offsets) return gfail(GFM_ERR_INVALID, "gfm_sequence_mutation_scan: NULL argument");
+    // ---- the sequences and their tiles
+    if (seq_offsets[0] < 0) return gfail(GFM_ERR_INVALID, "gfm_sequence_mutation_scan: seq_offsets descends below 0");
+    std::vector<MsTile> tiles;
+    for (int v = 0; v < n_seqs; ++v) {
+        const long long a = seq_offsets[v], b = seq_offsets[v + 1];
+        if (b < a) return gfail(GFM_ERR_INVALID, "gfm_sequence_mutation_scan: seq_offsets descends at sequence " + std::to_string(v));
+        if (b - a > 0x7fffffffll)
+            return gfail(GFM_ERR_INVALID, "gfm_sequence_mutation_scan: sequence " + std::to_string(v) + " holds 2^31 bases or more");
+        for (long long s = 0; s < b - a; s += kMsTile) tiles.push_back(MsTile{a, (int)(b - a), (int)s});
+    }
+    const long long n_bases = seq_offsets[n_seqs];
+    if (tiles.empty()) return GFM_OK;
+    if (!motifs || !d_weights || !d_keys || !d_sums || !d_status || !d_bases)
+        return gfail(GFM_ERR_INVALID, "gfm_sequence_mutation_scan: NULL argument");
+    int W = 0, mdev = -1;
+    std::vector<const unsigned *> ftab((size_t)n_motifs);
+    std::vector<int> min_val((size_t)n_motifs);
+    for (int m = 0; m < n_motifs; ++m) {
+        if (!motifs[m] || !d_weights[m] || !d_keys[m] || !d_sums[m]) return gfail(GFM_ERR_INVALID, "NULL motif / device buffer");
+        const int64_t *sm = nullptr;
+        int Wm = 0, L = 0, lo = 0, nb = 0, dev_m = 0, n_cu = 0;
+        const int rc = gfm_motif_view_(motifs[m], kFusedMaxBins[0], 0, &sm, &Wm, &min_val[(size_t)m], &L, &lo, &nb, &dev_m, &n_cu,
+                                       &ftab[(size_t)m]);
+        if (rc) return rc;
+        if (m == 0) { W = Wm; mdev = dev_m; }
+        else if (Wm != W || dev_m != mdev) return gfail(GFM_ERR_INVALID, "the motifs of one call have one width and live on one device");
+        if (min_val[(size_t)m] < 0 || min_val[(size_t)m] >= L || L > 65536)
+            return gfail(GFM_ERR_INVALID, "scores outside the packed table's 16 bits");
+    }
+    if (W < 1 || W > GFM_MAX_WIDTH) return gfail(GFM_ERR_INVALID, "width outside [1, 64]");
+    // the capacity of a sum: a side has at most W windows, each once per strand
+    if ((unsigned __int128)max_weight * 2u * (unsigned)W > (unsigned __int128)UINT64_MAX)
+        return gfail(GFM_ERR_INVALID, "gfm_sequence_mutation_scan: a side holds up to " + std::to_string(2 * W) +
+                                      " windows: with weights up to " + std::to_string((unsigned long long)max_weight) +
+                                      " a sum may pass 2^64 - 1");
+    {
+        int dev = -1;
+        GX_TRY(hipGetDevice(&dev));
+        if (dev != mdev) return gfail(GFM_ERR_INVALID, "the motif lives on another device than the current one");
+    }
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    GX_TRY(hipMemsetAsync(d_status, 0, sizeof(int32_t), st));
+    // ---- the scratch: the tile table (the host copy outlives the upload: the entry waits for the stream)
+    const size_t tile_bytes = align256(sizeof(MsTile) * tiles.size());
+    MsTile *d_tiles = nullptr;
+    GX_TRY(hipMallocAsync(reinterpret_cast<void **>(&d_tiles), tile_bytes, st));
+    hipError_t e = hipMemcpyAsync(d_tiles, tiles.data(), sizeof(MsTile) * tiles.size(), hipMemcpyHostToDevice, st);
+    const unsigned blocks = (unsigned)std::min<size_t>(tiles.size(), (size_t)kMsMaxBlocks);
+    const int fwd = (flags & GFM_GRAPH_FORWARD_ONLY) ? 1 : 0;
+    for (int m0 = 0; e == hipSuccess && m0 < n_motifs; m0 += kMsMotifs) {
+        const int mm = std::min(kMsMotifs, n_motifs - m0);
+        MsMotifs mt = {};
+        for (int k = 0; k < mm; ++k) {
+            mt.ftab[k] = ftab[(size_t)(m0 + k)];
+            mt.wtab[k] = reinterpret_cast<const unsigned long long *>(d_weights[m0 + k]);
+            mt.keys[k] = d_keys[m0 + k];
+            mt.sums[k] = reinterpret_cast<unsigned long long *>(d_sums[m0 + k]);
+            mt.min_val[k] = min_val[(size_t)(m0 + k)];
+        }
+        hipLaunchKernelGGL(mutation_scan_kernel, dim3(blocks, (unsigned)mm), dim3(kMsThreads), 0, st, d_tiles,
+                           (long long)tiles.size(), d_bases, n_bases, mt, W, fwd, d_status);
+        e = hipGetLastError();
+    }
+    int32_t verdict = 0;
+    if (e == hipSuccess) e = hipMemcpyAsync(&verdict, d_status, sizeof verdict, hipMemcpyDeviceToHost, st);
+    const hipError_t ef = hipFreeAsync(d_tiles, st);
+    const hipError_t es = hipStreamSynchronize(st);              // (also on failure: the tile table's host copy is still read)
+    if (e == hipSuccess) e = ef;
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) return gfail(GFM_ERR_HIP, std::string("gfm_sequence_mutation_scan: ") + hipGetErrorString(e));
+    if (verdict & kMsBadTile) return gfail(GFM_ERR_INVALID, "gfm_sequence_mutation_scan: a tile lies outside its sequence");
+    return GFM_OK;
+}

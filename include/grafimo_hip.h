@@ -859,6 +859,39 @@ int gfm_graph_query_edits(const gfm_motif_t *motifs, int32_t n_motifs, const uin
                           const int32_t *d_item_edit, uint32_t flags, gfm_edit_record_t *const *d_records, int32_t *d_status,
                           void *stream);
 
+/* ------------------------------------------------------------------ mutation scan: every single-base change of a spelled sequence
+ * Graph-independent.  THE RULE.  For a sequence x of n bases and a motif of width W, for every offset o in 0 .. n - 1 and every
+ * base b in A, C, G, T:
+ *   y = x with y[o] = b.
+ *   REF side: the window starts s of x with max(0, o - W + 1) <= s <= min(o, n - W).
+ *   ALT side: the same starts in y.
+ *   Every window is scored once per strand, or + only under GFM_GRAPH_FORWARD_ONLY.
+ *   A window that holds a base that is not A/C/G/T scores min_val on both strands.  Case is folded, as base_code does.
+ *   Per side: the best window by (score descending, s ascending, + before -), as the key
+ *   ((score + 1) << 8) | ((64 - (s - o)) << 1) | plus -- gfm_graph_query_edits' encoding, with s - o in -(W - 1) .. 0; key 0 means
+ *   the side has no window (n < W) --, and the exact uint64 sum of w[score] over the side's windows and strands.
+ *   b equal to the folded x[o] gives ALT equal to REF.
+ *   An x[o] that is no base has an all-min_val REF side, and each b can repair it.
+ * By construction the result for b != x[o] is field for field what gfm_graph_query_edits returns for the edit
+ * (coordinate of o, x[o], b) applied to x, wherever a coordinate names o.
+ *
+ * n_motifs motifs of ONE width on the current device, d_weights[m] uint64 [table length] per motif and max_weight, the largest
+ * weight of all tables (host): refused when max_weight * 2 * W passes 2^64 - 1.  seq_offsets: HOST, int64 [n_seqs + 1], ascending
+ * from seq_offsets[0] >= 0: the bases of sequence v are d_bases[seq_offsets[v] .. seq_offsets[v + 1]); empty sequences are
+ * allowed.  d_keys[m] uint32 [seq_offsets[n_seqs]][5] and d_sums[m] uint64 [seq_offsets[n_seqs]][5]: per base of d_bases the
+ * columns REF, A, C, G, T.  Every row of a sequence is written, nothing is zeroed by the caller.  d_status int32: a device
+ * word of the caller's, cleared and read here.
+ * The work is cut into (sequence, GFM_MUTSCAN_TILE offsets) tiles by the library; the result does not depend on the tile and
+ * a caller never needs it -- it is exported so that tests can aim at its edges.
+ * No sequence or no base returns GFM_OK and touches nothing.  GFM_ERR_INVALID: a NULL pointer, motifs of different widths or
+ * on another device than the current one, a width outside [1, 64], weights that can overflow a sum, offsets that descend, a
+ * sequence of 2^31 bases or more, an unknown flag.  The call WAITS for the stream (it reads the verdict of the device's
+ * check of the tile table). */
+#define GFM_MUTSCAN_TILE 64
+int gfm_sequence_mutation_scan(const gfm_motif_t *motifs, int32_t n_motifs, const uint64_t *const *d_weights, uint64_t max_weight,
+                               int32_t n_seqs, const int64_t *seq_offsets, const uint8_t *d_bases, uint32_t flags,
+                               uint32_t *const *d_keys, uint64_t *const *d_sums, int32_t *d_status, void *stream);
+
 /* ------------------------------------------------------------------ hit pairs: rows close to each other that share carriers
  * Graph-independent (csrc/hit_pairs.hip).  n rows (n < 2^31 - 1) in device memory, in ascending (d_group, d_lo) order:
  * d_group int32, d_lo <= d_hi int64 (|x| < 2^61), d_masks uint64 [n][hw] (hw >= 1 words of a bitset whose unused tail
