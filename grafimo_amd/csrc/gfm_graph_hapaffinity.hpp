@@ -1,7 +1,8 @@
 // gfm_graph_hapaffinity.hpp -- the per-haplotype total binding affinity: for every region of the caller's list and every
 // haplotype of the graph, the SUM over every k-mer of the haplotype's own sequence in the region of a 64-bit integer weight
 // looked up by the k-mer's scaled score (included at the end of graph_extract.hip behind gfm_graph_hapscores.hpp, whose
-// runs, limits and walk enumeration it shares).
+// runs, run shape, limits and walk enumeration it shares; it uses gfm_graph_table_score.hpp's window_sum, walk_value,
+// walk_code, walk_is_reference and ConstraintAt).
 //
 // Rows(r, h) are those of gfm_graph_hapscores.hpp.  A(r, h) = sum over Rows(r, h) of w[score(row)] in uint64: integer adds
 // commute, so the result is exact and depends neither on the run / block decomposition nor on the order of the atomics.
@@ -26,23 +27,6 @@
 //      plain store when the run is the region's only one, else a 64-bit atomicAdd.  Block 0 writes the reference column.
 namespace {
 
-// the value of lane `r` (wave-uniform) in every lane
-__device__ __forceinline__ unsigned long long ha_from_lane(unsigned long long v, int r)
-{
-    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, r);
-    const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(v >> 32), r);
-    return ((unsigned long long)hi << 32) | lo;
-}
-
-// what a walk adds: the weights of its two strands' scores (a k-mer holding N scores min_val).  Scores lie in [0, L): the
-// motif's matrix entries are within [0, 1000] (checked when the handle is made) and L = 1000 W + 1.
-__device__ __forceinline__ unsigned long long ha_walk_value(const unsigned long long *__restrict__ wtab, unsigned sum, int bad,
-                                                            int min_val, int forward_only)
-{
-    const unsigned long long vp = wtab[bad ? min_val : (int)(sum & 0xffffu)];
-    return forward_only ? vp : vp + wtab[bad ? min_val : (int)(sum >> 16)];
-}
-
 __global__ void __launch_bounds__(kHsThreads)
 graph_hapaffinity_kernel(GraphDev g, const unsigned *__restrict__ ftab, const unsigned long long *__restrict__ wtab, int W,
                          int min_val, const HsRun *__restrict__ runs, long long n_runs, int forward_only, int hb,
@@ -66,19 +50,11 @@ graph_hapaffinity_kernel(GraphDev g, const unsigned *__restrict__ ftab, const un
             const long long p = run.p0 + k;
             const int i0 = lower_bound_pos(g.pos, g.n_sites, p);
             bool plain = (i0 >= g.n_sites || (long long)g.pos[i0] >= p + W) && !covered_by_deletion(g, p, i0);
-            for (int j = i0 - 1; plain && j >= 0 && g.pos[j] == p - 1; --j)
-                if (g.ins_len[j] > 0) plain = false;
+            for (int j = i0 - 1; plain && j >= 0 && g.pos[j] == p - 1; --j)     // (graph_hapscore_kernel's test, kept in
+                if (g.ins_len[j] > 0) plain = false;                            // line: see gfm_graph_table_score.hpp)
             plain_win[k] = plain ? 1 : 0;
-            if (plain && p + W <= run.limit) {
-                unsigned sum = 0u;
-                int bad = 0;
-                for (int j = 0; j < W; ++j) {
-                    const unsigned c = base_code(g.ref[p + j]);
-                    sum += ftab[j * 8 + (c & 7u)];
-                    bad |= (int)(c >> 2);
-                }
-                all_s += ha_walk_value(wtab, sum, bad, min_val, forward_only);
-            }
+            if (plain && p + W <= run.limit)
+                all_s += walk_value(wtab, window_sum(ftab, W, [&](int j) { return base_code(g.ref[p + j]); }), min_val, forward_only);
         }
         __syncthreads();
         // ---- 2. + 3. the other windows, a wavefront each
@@ -98,33 +74,24 @@ graph_hapaffinity_kernel(GraphDev g, const unsigned *__restrict__ ftab, const un
                     unsigned long long value = 0ull;
                     if (q < prod) {
                         replay_walk<kHsMaxWalks>(g, p, W, i0, ws, st, q, prod, run.limit, em);
-                        unsigned sum = 0u;
-                        int bad = 0;
-                        for (int j = 0; j < W; ++j) {
-                            const unsigned c = base_code(src[j] >= 0 ? g.ref[src[j]] : km[j]);
-                            sum += ftab[j * 8 + (c & 7u)];
-                            bad |= (int)(c >> 2);
-                        }
-                        const unsigned long long v = ha_walk_value(wtab, sum, bad, min_val, forward_only);
+                        const WindowSum w = window_sum(ftab, W, [&](int j) { return walk_code(g, src, km, j); });
+                        const unsigned long long v = walk_value(wtab, w, min_val, forward_only);
                         if (em.n_cons == 0) {
                             all_s += v;                               // a walk over no site: everyone's
                         } else {
-                            bool ref = true;
-                            for (int c = 0; c < em.n_cons; ++c)
-                                if (em.get(c) & 3) ref = false;
-                            if (ref) ref_s += v;
+                            if (walk_is_reference(em)) ref_s += v;
                             nc = em.n_cons;
                             value = v;
                         }
                     }
                     if (!__builtin_amdgcn_ballot_w64(nc > 0)) continue;
-                    auto at = [&](int c, int &site, int &al) { const int v = em.get(c); site = v >> 4; al = v & 3; };
+                    const ConstraintAt at{em};
                     for (int w = 0; w < nw; ++w) {
                         const unsigned long long mine = nc > 0 ? carrier_word<true>(g, nc, at, w0 + w) : 0ull;
                         unsigned long long add = 0ull;
                         for (unsigned long long left = __builtin_amdgcn_ballot_w64(mine != 0ull); left; left &= left - 1ull) {
                             const int r = __ffsll((long long)left) - 1;
-                            const unsigned long long word = ha_from_lane(mine, r), v = ha_from_lane(value, r);
+                            const unsigned long long word = wave_readlane_ll(mine, r), v = wave_readlane_ll(value, r);
                             add += ((word >> lane) & 1ull) ? v : 0ull;     // (both read before the select: no cross-lane
                                                                            // read under a lane-divergent branch)
                         }
@@ -167,30 +134,20 @@ GFM_API int gfm_graph_haplotype_affinity(gfm_graph_t g, const gfm_motif_t *motif
     if (!motifs || n_motifs < 1 || n_regions < 0 || (n_regions && (!h_starts || !h_stops)) || !d_weights || !d_sums || !d_overflow)
         return gfail(GFM_ERR_INVALID, "bad argument");
     if (flags & ~(uint32_t)GFM_GRAPH_FORWARD_ONLY) return gfail(GFM_ERR_INVALID, "unknown flag");
-    if (windows_per_run < 0 || windows_per_run > kHsMaxRun)
-        return gfail(GFM_ERR_INVALID, "windows_per_run outside 0 .. " + std::to_string(kHsMaxRun));
-    if (haplotypes_per_block < 0 || haplotypes_per_block > kHsMaxBlockHaps || haplotypes_per_block % 64)
-        return gfail(GFM_ERR_INVALID, "haplotypes_per_block: 0 or a multiple of 64 up to " + std::to_string(kHsMaxBlockHaps));
-    int W = 0, mdev = -1;
-    std::vector<const unsigned *> ftab(n_motifs);
-    std::vector<int> min_val(n_motifs);
-    for (int m = 0; m < n_motifs; ++m) {
+    HsShape shape;
+    if (const int rc = hs_run_shape(g->dev.n_hap, windows_per_run, haplotypes_per_block, shape)) return rc;
+    for (int m = 0; m < n_motifs; ++m)
         if (!motifs[m] || !d_weights[m] || !d_sums[m]) return gfail(GFM_ERR_INVALID, "NULL motif / device buffer");
-        const int64_t *sm = nullptr;
-        int Wm = 0, L = 0, lo = 0, nb = 0, dev_m = 0, n_cu = 0;
-        const int rc = gfm_motif_view_(motifs[m], kFusedMaxBins[0], 0, &sm, &Wm, &min_val[m], &L, &lo, &nb, &dev_m, &n_cu, &ftab[m]);
-        if (rc) return rc;
-        if (m == 0) { W = Wm; mdev = dev_m; }
-        else if (Wm != W || dev_m != mdev) return gfail(GFM_ERR_INVALID, "the motifs of one call have one width and live on one device");
-        if (min_val[m] < 0 || min_val[m] >= L || L > 65536) return gfail(GFM_ERR_INVALID, "scores outside the packed table's 16 bits");
-    }
+    MotifSet ms;
+    if (const int rc = view_motif_set(motifs, n_motifs, ScoreBits::PackedTable, ms)) return rc;
+    const int W = ms.W;
+    if (const int rc = check_regions(n_regions, h_starts, h_stops)) return rc;
     // the capacity of a cell: a haplotype has at most one row per strand and base of its own sequence that starts in the
     // region -- the region's reference bases and, at most, every inserted base of the graph
     const long long ref_len = g->dev.ref_len;
     unsigned long long inserted = 0;
     for (const int il : g->host.ins_len) inserted += (unsigned long long)il;
     for (int r = 0; r < n_regions; ++r) {
-        if (h_stops[r] < h_starts[r]) return gfail(GFM_ERR_INVALID, "a region ends before it starts");
         const long long len = std::min<long long>(h_stops[r], ref_len) - std::max<long long>(h_starts[r], 0);
         if (len <= 0) continue;
         const unsigned __int128 rows_bound = (unsigned __int128)2 * ((unsigned __int128)len + inserted);
@@ -199,24 +156,17 @@ GFM_API int gfm_graph_haplotype_affinity(gfm_graph_t g, const gfm_motif_t *motif
                                           std::to_string((unsigned long long)rows_bound) + " rows per haplotype: with weights up "
                                           "to " + std::to_string((unsigned long long)max_weight) + " a sum may pass 2^64 - 1");
     }
-    {
-        int dev = -1;
-        GX_TRY(hipGetDevice(&dev));
-        if (dev != mdev) return gfail(GFM_ERR_INVALID, "the motif lives on another device than the current one");
-    }
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (const int rc = g->serialise(st)) return rc;
     long long n_runs = 0;
     if (const int rc = hs_stage_runs(g, n_regions, h_starts, h_stops, W, windows_per_run, st, &n_runs)) return rc;
     if (n_runs > 0) {
-        const int H = g->dev.n_hap, hb = hs_block_haplotypes(H, haplotypes_per_block);
-        const dim3 grid((unsigned)std::min<long long>(n_runs, 1 << 16), (unsigned)((H + hb - 1) / hb));
-        const int fwd = (flags & GFM_GRAPH_FORWARD_ONLY) ? 1 : 0;
+        const int fwd = (flags & GFM_GRAPH_FORWARD_ONLY) ? 1 : 0, hb = shape.hb;
         const HsRun *runs = static_cast<const HsRun *>(g->v_wins);
         for (int m = 0; m < n_motifs; ++m) {
-            hipLaunchKernelGGL(graph_hapaffinity_kernel, grid, dim3(kHsThreads), sizeof(unsigned long long) * (size_t)hb, st, g->dev,
-                               ftab[m], reinterpret_cast<const unsigned long long *>(d_weights[m]), W, min_val[m], runs, n_runs,
-                               fwd, hb, reinterpret_cast<unsigned long long *>(d_sums[m]), d_overflow);
+            hipLaunchKernelGGL(graph_hapaffinity_kernel, shape.grid(n_runs), dim3(kHsThreads), sizeof(unsigned long long) * (size_t)hb,
+                               st, g->dev, ms.ftab[m], reinterpret_cast<const unsigned long long *>(d_weights[m]), W, ms.min_val[m],
+                               runs, n_runs, fwd, hb, reinterpret_cast<unsigned long long *>(d_sums[m]), d_overflow);
             GX_TRY(hipGetLastError());
         }
     }

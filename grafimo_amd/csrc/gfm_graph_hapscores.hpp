@@ -1,7 +1,11 @@
 // gfm_graph_hapscores.hpp -- the per-haplotype best motif score: for every region of the caller's list and every haplotype
 // of the graph, the highest-scoring k-mer of the haplotype's own sequence in the region, with no threshold and no hit list
-// (included at the end of graph_extract.hip: it enumerates a window's walks as graph_variant_kernel does --
-// for_window_layouts, replay_walk -- and scores with the motif's packed two-strand table of the fused path).
+// (included at the end of graph_extract.hip behind gfm_graph_variant.hpp: it enumerates a window's walks as
+// graph_variant_kernel does -- for_window_layouts, replay_walk -- and scores with the motif's packed two-strand table of the
+// fused path.  This kernel keeps its OWN window loops, min_val selects and reference test instead of
+// gfm_graph_table_score.hpp's window_sum / strand_scores / walk_is_reference: with them it measured 0.4 % to 3.8 % slower than
+// the parent at a run-to-run spread of 0.01 ms in 14.7 -- profiles/table_entries_refactor_ab.txt; a change to the scoring
+// rule is made here as well as there).
 //
 // Rows(r, h) are the report's threshold-1 rows of region r whose walk haplotype h CARRIES (h is in the AND of the bitsets of
 // the walk's allele constraints, the set whose popcount is haplotype_frequency).  The best row is the one with the largest
@@ -69,7 +73,7 @@ __device__ inline void hs_carriers(const GraphDev &g, int w0, int nw, int n_rec,
             const int hl = w * 64 + lane;
             const unsigned long long cur = keys_lds[hl];        // (may be stale: the atomic settles it)
             if (!__builtin_amdgcn_ballot_w64(key > cur)) continue;
-            auto at = [&](int c, int &site, int &al) { const int v = pool[off + c]; site = v >> 4; al = v & 3; };
+            auto at = [&](int c, int &site, int &al) { unpack_constraint(pool[off + c], site, al); };
             const unsigned long long acc = carrier_word<true>(g, n, at, w0 + w);
             if (((acc >> lane) & 1ull) && key > cur) atomicMax(&keys_lds[hl], key);
         }
@@ -162,14 +166,10 @@ graph_hapscore_kernel(GraphDev g, const unsigned *__restrict__ ftab, int W, int 
                             q_n[wave][slot] = nc;
                             for (int c = 0; c < nc; ++c) q_pool[wave][ex - done + c] = em.get(c);
                         }
-                        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                        __builtin_amdgcn_wave_barrier();
-                        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                        wave_lds_sync();
                         hs_carriers(g, w0, nw, __popcll(bal), q_key[wave], q_off[wave], q_n[wave], q_pool[wave], hs_keys);
                         done = __shfl(incl, 63 - __clzll(bal));
-                        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                        __builtin_amdgcn_wave_barrier();
-                        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                        wave_lds_sync();
                     }
                 }
             });
@@ -220,26 +220,26 @@ static int hs_stage_runs(gfm_graph *g, int32_t n_regions, const int64_t *h_start
         }
     }
     *n_runs = (long long)(g->h_vwins.size() / kWords);
-    if (*n_runs > 0) {
-        const size_t n_vw = (size_t)*n_runs * (sizeof(HsRun) / sizeof(VarWin));
-        if (n_vw > g->v_cap) {
-            if (g->v_wins) GX_TRY(hipFree(g->v_wins));
-            g->v_wins = nullptr;
-            g->v_cap = 0;
-            GX_TRY(hipMalloc(&g->v_wins, sizeof(VarWin) * n_vw));
-            g->v_cap = n_vw;
-        }
-        GX_TRY(hipMemcpyAsync(g->v_wins, g->h_vwins.data(), sizeof(HsRun) * (size_t)*n_runs, hipMemcpyHostToDevice, st));
-    }
-    return GFM_OK;
+    return upload_vwins(g, st);
 }
 
-// haplotypes of one block: the caller's, or (0) as few blocks as the LDS allows, split evenly
-static int hs_block_haplotypes(int H, int haplotypes_per_block)
+// The run shape of a call of the two run entries, checked -> the haplotypes of one block (the caller's, or (0) as few blocks
+// as the LDS allows, split evenly) and the grid: the runs by the blocks of the graph's H haplotypes.
+struct HsShape {
+    int hb = 0;
+    unsigned blocks = 0;
+    dim3 grid(long long n_runs) const { return dim3((unsigned)std::min<long long>(n_runs, 1 << 16), blocks); }
+};
+static int hs_run_shape(int H, int32_t windows_per_run, int32_t haplotypes_per_block, HsShape &shape)
 {
-    if (haplotypes_per_block) return haplotypes_per_block;
+    if (windows_per_run < 0 || windows_per_run > kHsMaxRun)
+        return gfail(GFM_ERR_INVALID, "windows_per_run outside 0 .. " + std::to_string(kHsMaxRun));
+    if (haplotypes_per_block < 0 || haplotypes_per_block > kHsMaxBlockHaps || haplotypes_per_block % 64)
+        return gfail(GFM_ERR_INVALID, "haplotypes_per_block: 0 or a multiple of 64 up to " + std::to_string(kHsMaxBlockHaps));
     const int blocks = (H + kHsMaxBlockHaps - 1) / kHsMaxBlockHaps;
-    return ((H + blocks - 1) / blocks + 63) / 64 * 64;
+    shape.hb = haplotypes_per_block ? haplotypes_per_block : ((H + blocks - 1) / blocks + 63) / 64 * 64;
+    shape.blocks = (unsigned)((H + shape.hb - 1) / shape.hb);
+    return GFM_OK;
 }
 
 GFM_API int gfm_graph_haplotype_scores(gfm_graph_t g, const gfm_motif_t *motifs, int32_t n_motifs, int32_t n_regions,
@@ -251,28 +251,18 @@ GFM_API int gfm_graph_haplotype_scores(gfm_graph_t g, const gfm_motif_t *motifs,
     if (!motifs || n_motifs < 1 || n_regions < 0 || (n_regions && (!h_starts || !h_stops)) || !d_keys || !d_overflow)
         return gfail(GFM_ERR_INVALID, "bad argument");
     if (flags & ~(uint32_t)GFM_GRAPH_FORWARD_ONLY) return gfail(GFM_ERR_INVALID, "unknown flag");
-    if (windows_per_run < 0 || windows_per_run > kHsMaxRun)
-        return gfail(GFM_ERR_INVALID, "windows_per_run outside 0 .. " + std::to_string(kHsMaxRun));
-    if (haplotypes_per_block < 0 || haplotypes_per_block > kHsMaxBlockHaps || haplotypes_per_block % 64)
-        return gfail(GFM_ERR_INVALID, "haplotypes_per_block: 0 or a multiple of 64 up to " + std::to_string(kHsMaxBlockHaps));
-    int W = 0, mdev = -1;
-    std::vector<const unsigned *> ftab(n_motifs);
-    std::vector<int> min_val(n_motifs);
-    for (int m = 0; m < n_motifs; ++m) {
+    HsShape shape;
+    if (const int rc = hs_run_shape(g->dev.n_hap, windows_per_run, haplotypes_per_block, shape)) return rc;
+    for (int m = 0; m < n_motifs; ++m)
         if (!motifs[m] || !d_keys[m]) return gfail(GFM_ERR_INVALID, "NULL motif / device buffer");
-        const int64_t *sm = nullptr;
-        int Wm = 0, L = 0, lo = 0, nb = 0, dev_m = 0, n_cu = 0;
-        const int rc = gfm_motif_view_(motifs[m], kFusedMaxBins[0], 0, &sm, &Wm, &min_val[m], &L, &lo, &nb, &dev_m, &n_cu, &ftab[m]);
-        if (rc) return rc;
-        if (m == 0) { W = Wm; mdev = dev_m; }
-        else if (Wm != W || dev_m != mdev) return gfail(GFM_ERR_INVALID, "the motifs of one call have one width and live on one device");
-        if (min_val[m] < 0 || L > 65536) return gfail(GFM_ERR_INVALID, "scores outside the key's 16 bits");
-    }
+    MotifSet ms;
+    if (const int rc = view_motif_set(motifs, n_motifs, ScoreBits::Key, ms)) return rc;
+    const int W = ms.W;
+    if (const int rc = check_regions(n_regions, h_starts, h_stops)) return rc;
     // the key's coordinate fields: a region's start offsets below 2^28 - 1, a walk's span (at most W bases plus W - 1 jumped
     // deletions, and never beyond the region) within 2^19 - 1
     const long long ref_len = g->dev.ref_len, walk_span = (long long)W + (long long)(W - 1) * g->max_del_len;
     for (int r = 0; r < n_regions; ++r) {
-        if (h_stops[r] < h_starts[r]) return gfail(GFM_ERR_INVALID, "a region ends before it starts");
         const long long len = std::min<long long>(h_stops[r], ref_len) - std::max<long long>(h_starts[r], 0);
         if (len > kHsLeftMax)
             return gfail(GFM_ERR_INVALID, "gfm_graph_haplotype_scores: region " + std::to_string(r) + " is longer than 2^28 - 1 "
@@ -281,24 +271,17 @@ GFM_API int gfm_graph_haplotype_scores(gfm_graph_t g, const gfm_motif_t *motifs,
             return gfail(GFM_ERR_INVALID, "gfm_graph_haplotype_scores: a walk of region " + std::to_string(r) + " may span more "
                                           "than 2^19 - 1 bases (a deletion too long for the key's coordinate field)");
     }
-    {
-        int dev = -1;
-        GX_TRY(hipGetDevice(&dev));
-        if (dev != mdev) return gfail(GFM_ERR_INVALID, "the motif lives on another device than the current one");
-    }
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (const int rc = g->serialise(st)) return rc;
     long long n_runs = 0;
     if (const int rc = hs_stage_runs(g, n_regions, h_starts, h_stops, W, windows_per_run, st, &n_runs)) return rc;
     if (n_runs > 0) {
-        const int H = g->dev.n_hap, hb = hs_block_haplotypes(H, haplotypes_per_block);
-        const dim3 grid((unsigned)std::min<long long>(n_runs, 1 << 16), (unsigned)((H + hb - 1) / hb));
-        const int fwd = (flags & GFM_GRAPH_FORWARD_ONLY) ? 1 : 0;
+        const int fwd = (flags & GFM_GRAPH_FORWARD_ONLY) ? 1 : 0, hb = shape.hb;
         const HsRun *runs = static_cast<const HsRun *>(g->v_wins);
         for (int m = 0; m < n_motifs; ++m) {
-            hipLaunchKernelGGL(graph_hapscore_kernel, grid, dim3(kHsThreads), sizeof(unsigned long long) * (size_t)hb, st, g->dev,
-                               ftab[m], W, min_val[m], runs, n_runs, fwd, hb, reinterpret_cast<unsigned long long *>(d_keys[m]),
-                               d_overflow);
+            hipLaunchKernelGGL(graph_hapscore_kernel, shape.grid(n_runs), dim3(kHsThreads), sizeof(unsigned long long) * (size_t)hb,
+                               st, g->dev, ms.ftab[m], W, ms.min_val[m], runs, n_runs, fwd, hb,
+                               reinterpret_cast<unsigned long long *>(d_keys[m]), d_overflow);
             GX_TRY(hipGetLastError());
         }
     }

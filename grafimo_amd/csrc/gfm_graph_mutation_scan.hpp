@@ -1,6 +1,7 @@
 // gfm_graph_mutation_scan.hpp -- mutation scan: every single-base change at every offset of a spelled sequence, every window
 // the change touches scored before and after on both strands (included at the end of graph_extract.hip behind
-// gfm_graph_query_variants.hpp; it uses base_code, gfm_motif_view_, GX_TRY, gfail and align256).  Where query_edits_kernel
+// gfm_graph_query_variants.hpp; it uses base_code, view_motif_set, SeqMotifs, GX_TRY, gfail, align256 and
+// gfm_graph_table_score.hpp's window_sum, strand_scores, walk_value and edit_key).  Where query_edits_kernel
 // scores the 2 W windows of ONE edit with W lookups each, this kernel scores every window of a sequence ONCE and derives the
 // windows of all 4 n changes from the stored sums: an ALT window differs from its REF window in one table entry.
 //
@@ -36,7 +37,6 @@ constexpr int kMsTile = GFM_MUTSCAN_TILE, kMsThreads = kMsTile;
 constexpr int kMsHalo = GFM_MAX_WIDTH - 1;
 constexpr int kMsCodes = (kMsTile + 2 * kMsHalo + 15) & ~15;                        // 192
 constexpr int kMsWindows = (kMsTile + kMsHalo + 15) & ~15;                          // 128
-constexpr int kMsMotifs = 16;                                                        // motifs of one launch (grid.y)
 constexpr int kMsMaxBlocks = 1 << 16;
 constexpr int kMsBadTile = 1;
 
@@ -45,17 +45,14 @@ struct MsTile {
     int len, start;               // its length; the tile's first offset
 };
 
-struct MsMotifs {
-    const unsigned *ftab[kMsMotifs];
-    const unsigned long long *wtab[kMsMotifs];
-    unsigned *keys[kMsMotifs];
-    unsigned long long *sums[kMsMotifs];
-    int min_val[kMsMotifs];
+struct MsResults {
+    unsigned *keys[kSeqMotifs];
+    unsigned long long *sums[kSeqMotifs];
 };
 
 __global__ void __launch_bounds__(kMsThreads)
 mutation_scan_kernel(const MsTile *__restrict__ tiles, long long n_tiles, const uint8_t *__restrict__ bases, long long n_bases,
-                     MsMotifs mt, int W, int forward_only, int *__restrict__ status)
+                     SeqMotifs mt, MsResults res, int W, int forward_only, int *__restrict__ status)
 {
     __shared__ unsigned ftab_s[GFM_MAX_WIDTH * 8];
     __shared__ unsigned long long wref_s[kMsWindows];
@@ -64,9 +61,9 @@ mutation_scan_kernel(const MsTile *__restrict__ tiles, long long n_tiles, const 
     const int m = blockIdx.y, tid = threadIdx.x;
     for (int i = tid; i < W * 8; i += kMsThreads) ftab_s[i] = mt.ftab[m][i];
     const unsigned long long *__restrict__ wtab = mt.wtab[m];
-    unsigned *__restrict__ keys = mt.keys[m];
-    unsigned long long *__restrict__ sums = mt.sums[m];
-    const unsigned min_val = (unsigned)mt.min_val[m];
+    unsigned *__restrict__ keys = res.keys[m];
+    unsigned long long *__restrict__ sums = res.sums[m];
+    const int min_val = mt.min_val[m];
     const int halo = W - 1;
     for (long long t = blockIdx.x; t < n_tiles; t += gridDim.x) {
         const MsTile tile = tiles[t];
@@ -86,21 +83,11 @@ mutation_scan_kernel(const MsTile *__restrict__ tiles, long long n_tiles, const 
         __syncthreads();
         // ---- phase 1: every window start under the tile and its halo, once
         for (int k = tid; k < nt + halo; k += kMsThreads) {
-            unsigned acc = 0u, nb = 0u;
-            for (int j = 0; j < W; ++j) {
-                const unsigned c = code_s[k + j];
-                acc += ftab_s[j * 8 + c];
-                nb += c >> 2;
-            }
+            const WindowSum w = window_sum(ftab_s, W, [&](int j) { return (unsigned)code_s[k + j]; });
             const int s = c0 + k;
-            unsigned long long wr = 0ull;
-            if (s >= 0 && s <= len - W) {
-                wr = wtab[nb ? min_val : (acc & 0xffffu)];
-                if (!forward_only) wr += wtab[nb ? min_val : (acc >> 16)];
-            }
-            wsum_s[k] = acc;
-            bad_s[k] = (unsigned char)nb;
-            wref_s[k] = wr;
+            wsum_s[k] = w.sum;
+            bad_s[k] = (unsigned char)w.bad;
+            wref_s[k] = (s >= 0 && s <= len - W) ? walk_value(wtab, w, min_val, forward_only) : 0ull;
         }
         __syncthreads();
         // ---- phase 2: a thread per offset; the starts s = o - j of the sequence's windows over o
@@ -112,26 +99,21 @@ mutation_scan_kernel(const MsTile *__restrict__ tiles, long long n_tiles, const 
             const int j_lo = max(0, o - (len - W)), j_hi = min(halo, o);
             for (int j = j_lo; j <= j_hi; ++j) {
                 const int k = tid + halo - j;
-                const unsigned acc = wsum_s[k], nb = bad_s[k];
-                const unsigned place = (unsigned)(64 + j) << 1;   // 64 - (s - o): an earlier start is larger
-                const unsigned rf = nb ? min_val : (acc & 0xffffu);
-                key_r = max(key_r, ((rf + 1u) << 8) | place | 1u);
-                if (!forward_only) key_r = max(key_r, (((nb ? min_val : (acc >> 16)) + 1u) << 8) | place);
+                const WindowSum w{wsum_s[k], bad_s[k]};
+                const StrandScores rs = strand_scores(w, min_val);
+                key_r = max(key_r, edit_key(rs.plus, -j, true));  // (the window starts at s = o - j)
+                if (!forward_only) key_r = max(key_r, edit_key(rs.minus, -j, false));
                 sum_r += wref_s[k];
-                const bool valid = nb == xbad;                    // (no base of the window but x[o] itself is none)
-                const unsigned rest = acc - ftab_s[j * 8 + xo];
+                const unsigned invalid = w.bad - xbad;            // (0: no base of the window but x[o] itself is none)
+                const unsigned rest = w.sum - ftab_s[j * 8 + xo];
 #pragma unroll
                 for (unsigned b = 0; b < 4; ++b) {
                     if (b == xo) continue;                        // the REF column: copied below
-                    const unsigned v = rest + ftab_s[j * 8 + b];
-                    const unsigned sf = valid ? (v & 0xffffu) : min_val;
-                    key_b[b] = max(key_b[b], ((sf + 1u) << 8) | place | 1u);
-                    sum_b[b] += wtab[sf];
-                    if (!forward_only) {
-                        const unsigned sr = valid ? (v >> 16) : min_val;
-                        key_b[b] = max(key_b[b], ((sr + 1u) << 8) | place);
-                        sum_b[b] += wtab[sr];
-                    }
+                    const WindowSum wb{rest + ftab_s[j * 8 + b], invalid};
+                    const StrandScores as = strand_scores(wb, min_val);
+                    key_b[b] = max(key_b[b], edit_key(as.plus, -j, true));
+                    if (!forward_only) key_b[b] = max(key_b[b], edit_key(as.minus, -j, false));
+                    sum_b[b] += walk_value(wtab, wb, min_val, forward_only);
                 }
             }
 #pragma unroll
@@ -171,32 +153,16 @@ GFM_API int gfm_sequence_mutation_scan(const gfm_motif_t *motifs, int32_t n_moti
     if (tiles.empty()) return GFM_OK;
     if (!motifs || !d_weights || !d_keys || !d_sums || !d_status || !d_bases)
         return gfail(GFM_ERR_INVALID, "gfm_sequence_mutation_scan: NULL argument");
-    int W = 0, mdev = -1;
-    std::vector<const unsigned *> ftab((size_t)n_motifs);
-    std::vector<int> min_val((size_t)n_motifs);
-    for (int m = 0; m < n_motifs; ++m) {
+    for (int m = 0; m < n_motifs; ++m)
         if (!motifs[m] || !d_weights[m] || !d_keys[m] || !d_sums[m]) return gfail(GFM_ERR_INVALID, "NULL motif / device buffer");
-        const int64_t *sm = nullptr;
-        int Wm = 0, L = 0, lo = 0, nb = 0, dev_m = 0, n_cu = 0;
-        const int rc = gfm_motif_view_(motifs[m], kFusedMaxBins[0], 0, &sm, &Wm, &min_val[(size_t)m], &L, &lo, &nb, &dev_m, &n_cu,
-                                       &ftab[(size_t)m]);
-        if (rc) return rc;
-        if (m == 0) { W = Wm; mdev = dev_m; }
-        else if (Wm != W || dev_m != mdev) return gfail(GFM_ERR_INVALID, "the motifs of one call have one width and live on one device");
-        if (min_val[(size_t)m] < 0 || min_val[(size_t)m] >= L || L > 65536)
-            return gfail(GFM_ERR_INVALID, "scores outside the packed table's 16 bits");
-    }
-    if (W < 1 || W > GFM_MAX_WIDTH) return gfail(GFM_ERR_INVALID, "width outside [1, 64]");
+    MotifSet ms;
+    if (const int rc = view_motif_set(motifs, n_motifs, ScoreBits::PackedTable, ms)) return rc;
+    const int W = ms.W;
     // the capacity of a sum: a side has at most W windows, each once per strand
     if ((unsigned __int128)max_weight * 2u * (unsigned)W > (unsigned __int128)UINT64_MAX)
         return gfail(GFM_ERR_INVALID, "gfm_sequence_mutation_scan: a side holds up to " + std::to_string(2 * W) +
                                       " windows: with weights up to " + std::to_string((unsigned long long)max_weight) +
                                       " a sum may pass 2^64 - 1");
-    {
-        int dev = -1;
-        GX_TRY(hipGetDevice(&dev));
-        if (dev != mdev) return gfail(GFM_ERR_INVALID, "the motif lives on another device than the current one");
-    }
     hipStream_t st = static_cast<hipStream_t>(stream);
     GX_TRY(hipMemsetAsync(d_status, 0, sizeof(int32_t), st));
     // ---- the scratch: the tile table (the host copy outlives the upload: the entry waits for the stream)
@@ -206,18 +172,15 @@ GFM_API int gfm_sequence_mutation_scan(const gfm_motif_t *motifs, int32_t n_moti
     hipError_t e = hipMemcpyAsync(d_tiles, tiles.data(), sizeof(MsTile) * tiles.size(), hipMemcpyHostToDevice, st);
     const unsigned blocks = (unsigned)std::min<size_t>(tiles.size(), (size_t)kMsMaxBlocks);
     const int fwd = (flags & GFM_GRAPH_FORWARD_ONLY) ? 1 : 0;
-    for (int m0 = 0; e == hipSuccess && m0 < n_motifs; m0 += kMsMotifs) {
-        const int mm = std::min(kMsMotifs, n_motifs - m0);
-        MsMotifs mt = {};
+    for (int m0 = 0; e == hipSuccess && m0 < n_motifs; m0 += kSeqMotifs) {
+        const int mm = std::min(kSeqMotifs, n_motifs - m0);
+        MsResults res = {};
         for (int k = 0; k < mm; ++k) {
-            mt.ftab[k] = ftab[(size_t)(m0 + k)];
-            mt.wtab[k] = reinterpret_cast<const unsigned long long *>(d_weights[m0 + k]);
-            mt.keys[k] = d_keys[m0 + k];
-            mt.sums[k] = reinterpret_cast<unsigned long long *>(d_sums[m0 + k]);
-            mt.min_val[k] = min_val[(size_t)(m0 + k)];
+            res.keys[k] = d_keys[m0 + k];
+            res.sums[k] = reinterpret_cast<unsigned long long *>(d_sums[m0 + k]);
         }
         hipLaunchKernelGGL(mutation_scan_kernel, dim3(blocks, (unsigned)mm), dim3(kMsThreads), 0, st, d_tiles,
-                           (long long)tiles.size(), d_bases, n_bases, mt, W, fwd, d_status);
+                           (long long)tiles.size(), d_bases, n_bases, seq_motifs(ms, d_weights, m0, mm), res, W, fwd, d_status);
         e = hipGetLastError();
     }
     int32_t verdict = 0;

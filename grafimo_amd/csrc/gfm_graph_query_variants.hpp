@@ -1,7 +1,8 @@
 // gfm_graph_query_variants.hpp -- query variants: an edit (REF -> ALT at a reference position) applied to a spelled sequence,
 // every window the edit touches scored before and after on both strands (included at the end of graph_extract.hip behind
-// gfm_graph_hapsequences.hpp, whose sequences -- bases and coordinates -- it reads; it uses base_code, gfm_motif_view_, GX_TRY,
-// gfail and the wave reductions).  The only kernel here that scores a sequence that is NOT a walk of the graph.
+// gfm_graph_hapsequences.hpp, whose sequences -- bases and coordinates -- it reads; it uses base_code, view_motif_set, SeqMotifs,
+// GX_TRY, gfail, the wave helpers and gfm_graph_table_score.hpp's window_sum, strand_scores, walk_value and edit_key).  The
+// first kernel here that scores a sequence that is NOT a walk of the graph.
 //
 // THE RULE (include/grafimo_hip.h states it for the library; tests/query_variant_bruteforce.py on the host).  A sequence x has
 // per base a coordinate, ~coordinate for an inserted base (gfm_graph_haplotype_sequences' d_coord).  An edit is (pos0, ref of
@@ -31,15 +32,9 @@ namespace {
 constexpr int kQvThreads = 256, kQvWaves = kQvThreads / 64;
 constexpr int kQvContext = 2 * (GFM_MAX_WIDTH - 1) + GFM_QUERY_MAX_ALLELE;          // 190
 constexpr int kQvSlice = (kQvContext + 15) & ~15;
-constexpr int kQvMotifs = 16;                                                        // motifs of one launch (grid.y)
 constexpr int kQvBadItem = 1, kQvBadEdit = 2, kQvBadSeq = 4;
 
-struct QvMotifs {
-    const unsigned *ftab[kQvMotifs];
-    const unsigned long long *wtab[kQvMotifs];
-    gfm_edit_record_t *rec[kQvMotifs];
-    int min_val[kQvMotifs];
-};
+struct QvRecords { gfm_edit_record_t *rec[kSeqMotifs]; };
 
 struct QvInput {
     int n_seqs, n_edits;
@@ -53,23 +48,8 @@ struct QvInput {
     const int *item_seq, *item_edit;
 };
 
-__device__ __forceinline__ int qv_wave_max(int v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = max(v, __shfl_xor(v, off));
-    return v;
-}
-
-// what the lanes wrote to the wave's LDS slice is read by other lanes of the wave (and the other way round)
-__device__ __forceinline__ void qv_wave_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 __global__ void __launch_bounds__(kQvThreads)
-query_edits_kernel(QvInput in, QvMotifs mt, int W, int forward_only, int *__restrict__ status)
+query_edits_kernel(QvInput in, SeqMotifs mt, QvRecords recs, int W, int forward_only, int *__restrict__ status)
 {
     __shared__ unsigned ftab_s[GFM_MAX_WIDTH * 8];
     __shared__ unsigned char slices[kQvWaves][2][kQvSlice];
@@ -78,7 +58,7 @@ query_edits_kernel(QvInput in, QvMotifs mt, int W, int forward_only, int *__rest
     __syncthreads();
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const unsigned long long *__restrict__ wtab = mt.wtab[m];
-    gfm_edit_record_t *__restrict__ out = mt.rec[m];
+    gfm_edit_record_t *__restrict__ out = recs.rec[m];
     const int min_val = mt.min_val[m];
     unsigned char *cx = slices[wave][0], *cy = slices[wave][1];
     for (long long it = (long long)blockIdx.x * kQvWaves + wave; it < in.n_items; it += (long long)gridDim.x * kQvWaves) {
@@ -122,8 +102,8 @@ query_edits_kernel(QvInput in, QvMotifs mt, int W, int forward_only, int *__rest
             if (c == p0 - 1) fp = j;
             cnt += (c >= p0 && c < p0 + lr) ? 1 : 0;
         }
-        fn = qv_wave_max(fn);
-        fp = qv_wave_max(fp);
+        fn = wave_max(fn);
+        fp = wave_max(fp);
         cnt = wave_sum(cnt);
         int st, o = fn;
         if (lr > 0) {
@@ -157,13 +137,13 @@ query_edits_kernel(QvInput in, QvMotifs mt, int W, int forward_only, int *__rest
         // ---- the used context of x and the same stretch of y, as base codes, in the wave's slice
         const int lo = max(0, o - (W - 1)), hi = min(len, o + lr + W - 1);
         const int oc = o - lo, nx = hi - lo, ny = nx - lr + la;
-        qv_wave_sync();                                      // (the last item's windows are read)
+        wave_lds_sync();                                     // (the last item's windows are read)
         for (int j = lane; j < nx; j += 64) cx[j] = (unsigned char)base_code(x[lo + j]);
         for (int j = lane; j < ny; j += 64) {
             const unsigned c = j < oc ? x[lo + j] : j < oc + la ? in.alt_bytes[ao + (j - oc)] : x[lo + j - la + lr];
             cy[j] = (unsigned char)base_code(c);
         }
-        qv_wave_sync();
+        wave_lds_sync();
         // ---- the windows of both sides: starts 0 .. min(oc + l - 1, n - W) of the slice (oc <= W - 1: every start from 0 on
         // reaches o), the lanes take them 64 at a time
         for (int side = 0; side < 2; ++side) {
@@ -173,23 +153,13 @@ query_edits_kernel(QvInput in, QvMotifs mt, int W, int forward_only, int *__rest
             unsigned key = 0u;
             unsigned long long sum = 0ull;
             for (int s = lane; s <= s_hi; s += 64) {
-                unsigned acc = 0u, nb = 0u;
-                for (int j = 0; j < W; ++j) {
-                    const unsigned c = buf[s + j];
-                    acc += ftab_s[j * 8 + (c & 7u)];
-                    nb |= c >> 2;
-                }
-                const unsigned place = (unsigned)(64 - (s - oc)) << 1;        // s - o in -63 .. 63: an earlier start is larger
-                const unsigned sf = nb ? (unsigned)min_val : (acc & 0xffffu);
-                key = max(key, ((sf + 1u) << 8) | place | 1u);
-                sum += wtab[sf];
-                if (!forward_only) {
-                    const unsigned sr = nb ? (unsigned)min_val : (acc >> 16);
-                    key = max(key, ((sr + 1u) << 8) | place);
-                    sum += wtab[sr];
-                }
+                const WindowSum w = window_sum(ftab_s, W, [&](int j) { return (unsigned)buf[s + j]; });
+                const StrandScores sc = strand_scores(w, min_val);
+                key = max(key, edit_key(sc.plus, s - oc, true));              // s - o in -63 .. 63
+                if (!forward_only) key = max(key, edit_key(sc.minus, s - oc, false));
+                sum += walk_value(wtab, w, min_val, forward_only);
             }
-            key = (unsigned)qv_wave_max((int)key);            // (below 2^25: the order of the ints is the order of the keys)
+            key = (unsigned)wave_max((int)key);               // (below 2^25: the order of the ints is the order of the keys)
             sum = (unsigned long long)wave_sum_ll((long long)sum);
             if (side) { rec.alt_key = key; rec.alt_sum = sum; }
             else { rec.ref_key = key; rec.ref_sum = sum; }
@@ -213,32 +183,16 @@ GFM_API int gfm_graph_query_edits(const gfm_motif_t *motifs, int32_t n_motifs, c
     if (!motifs || !d_weights || !d_records || !d_status || !d_seq_offsets || !d_bases || !d_coord || !d_pos0 || !d_ref_off ||
         !d_ref_bytes || !d_alt_off || !d_alt_bytes || !d_item_seq || !d_item_edit)
         return gfail(GFM_ERR_INVALID, "gfm_graph_query_edits: NULL argument");
-    int W = 0, mdev = -1;
-    std::vector<const unsigned *> ftab((size_t)n_motifs);
-    std::vector<int> min_val((size_t)n_motifs);
-    for (int m = 0; m < n_motifs; ++m) {
+    for (int m = 0; m < n_motifs; ++m)
         if (!motifs[m] || !d_weights[m] || !d_records[m]) return gfail(GFM_ERR_INVALID, "NULL motif / device buffer");
-        const int64_t *sm = nullptr;
-        int Wm = 0, L = 0, lo = 0, nb = 0, dev_m = 0, n_cu = 0;
-        const int rc = gfm_motif_view_(motifs[m], kFusedMaxBins[0], 0, &sm, &Wm, &min_val[(size_t)m], &L, &lo, &nb, &dev_m, &n_cu,
-                                       &ftab[(size_t)m]);
-        if (rc) return rc;
-        if (m == 0) { W = Wm; mdev = dev_m; }
-        else if (Wm != W || dev_m != mdev) return gfail(GFM_ERR_INVALID, "the motifs of one call have one width and live on one device");
-        if (min_val[(size_t)m] < 0 || min_val[(size_t)m] >= L || L > 65536)
-            return gfail(GFM_ERR_INVALID, "scores outside the packed table's 16 bits");
-    }
-    if (W < 1 || W > GFM_MAX_WIDTH) return gfail(GFM_ERR_INVALID, "width outside [1, 64]");
+    MotifSet ms;
+    if (const int rc = view_motif_set(motifs, n_motifs, ScoreBits::PackedTable, ms)) return rc;
+    const int W = ms.W;
     // the capacity of a sum: a side has at most W + 63 windows, each once per strand
     if ((unsigned __int128)max_weight * 2u * (unsigned)(W + GFM_QUERY_MAX_ALLELE) > (unsigned __int128)UINT64_MAX)
         return gfail(GFM_ERR_INVALID, "gfm_graph_query_edits: a side holds up to " + std::to_string(2 * (W + GFM_QUERY_MAX_ALLELE)) +
                                       " windows: with weights up to " + std::to_string((unsigned long long)max_weight) +
                                       " a sum may pass 2^64 - 1");
-    {
-        int dev = -1;
-        GX_TRY(hipGetDevice(&dev));
-        if (dev != mdev) return gfail(GFM_ERR_INVALID, "the motif lives on another device than the current one");
-    }
     hipStream_t st = static_cast<hipStream_t>(stream);
     GX_TRY(hipMemsetAsync(d_status, 0, sizeof(int32_t), st));
     QvInput in;
@@ -257,16 +211,12 @@ GFM_API int gfm_graph_query_edits(const gfm_motif_t *motifs, int32_t n_motifs, c
     in.item_edit = d_item_edit;
     const unsigned blocks = (unsigned)std::min<long long>((n_items + kQvWaves - 1) / kQvWaves, 1 << 15);
     const int fwd = (flags & GFM_GRAPH_FORWARD_ONLY) ? 1 : 0;
-    for (int m0 = 0; m0 < n_motifs; m0 += kQvMotifs) {
-        const int mm = std::min(kQvMotifs, n_motifs - m0);
-        QvMotifs mt = {};
-        for (int k = 0; k < mm; ++k) {
-            mt.ftab[k] = ftab[(size_t)(m0 + k)];
-            mt.wtab[k] = reinterpret_cast<const unsigned long long *>(d_weights[m0 + k]);
-            mt.rec[k] = d_records[m0 + k];
-            mt.min_val[k] = min_val[(size_t)(m0 + k)];
-        }
-        hipLaunchKernelGGL(query_edits_kernel, dim3(blocks, (unsigned)mm), dim3(kQvThreads), 0, st, in, mt, W, fwd, d_status);
+    for (int m0 = 0; m0 < n_motifs; m0 += kSeqMotifs) {
+        const int mm = std::min(kSeqMotifs, n_motifs - m0);
+        QvRecords recs = {};
+        for (int k = 0; k < mm; ++k) recs.rec[k] = d_records[m0 + k];
+        hipLaunchKernelGGL(query_edits_kernel, dim3(blocks, (unsigned)mm), dim3(kQvThreads), 0, st, in,
+                           seq_motifs(ms, d_weights, m0, mm), recs, W, fwd, d_status);
         GX_TRY(hipGetLastError());
     }
     int32_t verdict = 0;

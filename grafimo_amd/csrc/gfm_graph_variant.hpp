@@ -1,6 +1,7 @@
 // gfm_graph_variant.hpp -- per-variant motif effects: the best REF and the best ALT k-mer of every (site, allele) of the graph
-// (included at the end of graph_extract.hip: it walks the graph with the machinery the extraction kernels share --
-// simulate(), DelEmit, for_covering_deletions, allele_word -- and scores with the motif's packed table of the fused path).
+// (included at the end of graph_extract.hip behind gfm_graph_table_score.hpp, whose window_sum and ConstraintAt it uses: it
+// walks the graph with the machinery the extraction kernels share -- simulate(), DelEmit, for_covering_deletions,
+// allele_word -- and scores with the motif's packed table of the fused path).
 //
 // What a k-mer qualifies for: the (site, allele) pairs its walk carries a haplotype CONSTRAINT for in the existing counting
 // (DelEmit: a substitution base it reads, an insertion it reads or passes by, a deletion it jumps or whose bases it uses,
@@ -113,21 +114,15 @@ graph_variant_kernel(GraphDev g, const unsigned *__restrict__ ftab, int W, int m
                 DelEmit em(g, km, kr, src, W, more);
                 const long long end = replay_walk<kVarMaxWalks>(g, p, W, i0, ws, st, q, prod, limit, em);
                 if (em.n_cons == 0) continue;  // a walk over no site: no allele's footprint
-                unsigned sum = 0u;
-                int bad = 0;
-                for (int j = 0; j < W; ++j) {
+                const StrandScores ss = strand_scores(window_sum(ftab, W, [&](int j) {        // (and the k-mers are completed)
                     if (src[j] >= 0) {
                         km[j] = g.ref[src[j]];
                         kr[W - 1 - j] = complement(km[j]);
                     }
-                    const unsigned c = base_code(km[j]);
-                    sum += ftab[j * 8 + (c & 7u)];
-                    bad |= (int)(c >> 2);
-                }
-                int sc[2];
-                sc[0] = bad ? min_val : (int)(sum & 0xffffu);
-                sc[1] = bad ? min_val : (int)(sum >> 16);
-                auto at = [&](int kk, int &site, int &al) { const int v = em.get(kk); site = v >> 4; al = v & 3; };
+                    return base_code(km[j]);
+                }), min_val);
+                const int sc[2] = {ss.plus, ss.minus};
+                const ConstraintAt at{em};
                 int present = keep_zero ? 1 : -1;      // -1: not tested yet
                 for (int sd = 0; sd < (forward_only ? 1 : 2); ++sd) {
                     const long long start = sd ? end : p, stop = sd ? p : end;
@@ -165,6 +160,23 @@ graph_variant_kernel(GraphDev g, const unsigned *__restrict__ ftab, int W, int m
 
 }  // namespace
 
+// g->h_vwins, the window (or run) list of a call, into g->v_wins on `st`; the buffer grows to hold it
+static int upload_vwins(gfm_graph_t g, hipStream_t st)
+{
+    static_assert(sizeof(VarWin) == 2 * sizeof(long long), "h_vwins holds (p, limit) pairs");
+    const size_t n_vw = g->h_vwins.size() / 2;
+    if (n_vw == 0) return GFM_OK;
+    if (n_vw > g->v_cap) {
+        if (g->v_wins) GX_TRY(hipFree(g->v_wins));
+        g->v_wins = nullptr;
+        g->v_cap = 0;
+        GX_TRY(hipMalloc(&g->v_wins, sizeof(VarWin) * n_vw));
+        g->v_cap = n_vw;
+    }
+    GX_TRY(hipMemcpyAsync(g->v_wins, g->h_vwins.data(), sizeof(VarWin) * n_vw, hipMemcpyHostToDevice, st));
+    return GFM_OK;
+}
+
 // The windows within reach of a site: starts in [pos - W + 1, pos + 1 + del_len] (a walk that starts inside an insertion
 // anchored at p - 1, on bases a deletion anchored before p removes), merged, cut to every region's window range -> *n_win
 // (start, limit) pairs at g->v_wins, uploaded on `st`.  `unique`: a start that several regions hold is listed once, with the
@@ -197,25 +209,13 @@ static int variant_stage_windows(gfm_graph_t g, int W, int n_regions, const int6
             }
     }
     if (unique && !g->h_vwins.empty()) {
-        static_assert(sizeof(VarWin) == 2 * sizeof(long long), "h_vwins holds (p, limit) pairs");
         VarWin *b = reinterpret_cast<VarWin *>(g->h_vwins.data()), *e = b + g->h_vwins.size() / 2;
         std::sort(b, e, [](const VarWin &x, const VarWin &y) { return x.p != y.p ? x.p < y.p : x.limit > y.limit; });
         e = std::unique(b, e, [](const VarWin &x, const VarWin &y) { return x.p == y.p; });
         g->h_vwins.resize(2 * (size_t)(e - b));
     }
-    const long long n_win = (long long)(g->h_vwins.size() / 2);
-    *n_win_out = n_win;
-    if (n_win > 0) {
-        if ((size_t)n_win > g->v_cap) {
-            if (g->v_wins) GX_TRY(hipFree(g->v_wins));
-            g->v_wins = nullptr;
-            g->v_cap = 0;
-            GX_TRY(hipMalloc(&g->v_wins, sizeof(VarWin) * (size_t)n_win));
-            g->v_cap = (size_t)n_win;
-        }
-        GX_TRY(hipMemcpyAsync(g->v_wins, g->h_vwins.data(), sizeof(VarWin) * (size_t)n_win, hipMemcpyHostToDevice, st));
-    }
-    return GFM_OK;
+    *n_win_out = (long long)(g->h_vwins.size() / 2);
+    return upload_vwins(g, st);
 }
 
 GFM_API int gfm_graph_variant_effects(gfm_graph_t g, const gfm_motif_t *motifs, int32_t n_motifs, int32_t n_regions,
@@ -227,30 +227,16 @@ GFM_API int gfm_graph_variant_effects(gfm_graph_t g, const gfm_motif_t *motifs, 
         return gfail(GFM_ERR_INVALID, "bad argument");
     if (!d_keys || !d_recs || !rec_capacity || !d_rec_count || !d_overflow) return gfail(GFM_ERR_INVALID, "NULL argument array");
     if (flags & ~(uint32_t)(GFM_GRAPH_FORWARD_ONLY | GFM_VARIANT_KEEP_ZERO_FREQ)) return gfail(GFM_ERR_INVALID, "unknown flag");
-    int W = 0, mdev = -1;
-    std::vector<const unsigned *> ftab(n_motifs);
-    std::vector<int> min_val(n_motifs);
-    for (int m = 0; m < n_motifs; ++m) {
+    for (int m = 0; m < n_motifs; ++m)
         if (!motifs[m] || !d_keys[m] || !d_rec_count[m] || rec_capacity[m] < 0 || (rec_capacity[m] && !d_recs[m]))
             return gfail(GFM_ERR_INVALID, "NULL motif / device buffer");
-        const int64_t *sm = nullptr;
-        int Wm = 0, L = 0, lo = 0, nb = 0, dev_m = 0, n_cu = 0;
-        const int rc = gfm_motif_view_(motifs[m], kFusedMaxBins[0], 0, &sm, &Wm, &min_val[m], &L, &lo, &nb, &dev_m, &n_cu, &ftab[m]);
-        if (rc) return rc;
-        if (m == 0) { W = Wm; mdev = dev_m; }
-        else if (Wm != W || dev_m != mdev) return gfail(GFM_ERR_INVALID, "the motifs of one call have one width and live on one device");
-        if (min_val[m] < 0 || L > 65536) return gfail(GFM_ERR_INVALID, "scores outside the key's 16 bits");
-    }
-    for (int r = 0; r < n_regions; ++r)
-        if (h_stops[r] < h_starts[r]) return gfail(GFM_ERR_INVALID, "a region ends before it starts");
+    MotifSet ms;
+    if (const int rc = view_motif_set(motifs, n_motifs, ScoreBits::Key, ms)) return rc;
+    const int W = ms.W;
+    if (const int rc = check_regions(n_regions, h_starts, h_stops)) return rc;
     // a window's walks end within W bases plus the deletions they jump of their start: the key's coordinate fields hold that
     if ((long long)W * (g->max_del_len + 1) + W >= kVarStopBias)
         return gfail(GFM_ERR_INVALID, "a deletion too long for the variant table's coordinate fields");
-    {
-        int dev = -1;
-        GX_TRY(hipGetDevice(&dev));
-        if (dev != mdev) return gfail(GFM_ERR_INVALID, "the motif lives on another device than the current one");
-    }
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (const int rc = g->serialise(st)) return rc;
     long long n_win = 0;
@@ -264,10 +250,10 @@ GFM_API int gfm_graph_variant_effects(gfm_graph_t g, const gfm_motif_t *motifs, 
             unsigned long long *keys = reinterpret_cast<unsigned long long *>(d_keys[m]);
             unsigned long long *cnt = reinterpret_cast<unsigned long long *>(d_rec_count[m]);
             gfm_variant_rec_t *recs = static_cast<gfm_variant_rec_t *>(d_recs[m]);
-            hipLaunchKernelGGL(graph_variant_kernel<false>, dim3(grid), dim3(kVarThreads), 0, st, g->dev, ftab[m], W, min_val[m],
+            hipLaunchKernelGGL(graph_variant_kernel<false>, dim3(grid), dim3(kVarThreads), 0, st, g->dev, ms.ftab[m], W, ms.min_val[m],
                                wins, n_win, fwd, keep0, keys, recs, cnt, (long long)rec_capacity[m], d_overflow);
             GX_TRY(hipGetLastError());
-            hipLaunchKernelGGL(graph_variant_kernel<true>, dim3(grid), dim3(kVarThreads), 0, st, g->dev, ftab[m], W, min_val[m],
+            hipLaunchKernelGGL(graph_variant_kernel<true>, dim3(grid), dim3(kVarThreads), 0, st, g->dev, ms.ftab[m], W, ms.min_val[m],
                                wins, n_win, fwd, keep0, keys, recs, cnt, (long long)rec_capacity[m], d_overflow);
             GX_TRY(hipGetLastError());
         }

@@ -2,7 +2,7 @@
 // of the allele's carriers over the allele's footprint -- the sum, over every k-mer of every haplotype's own sequence that
 // covers the footprint, of a 64-bit integer weight looked up by the k-mer's scaled score -- beside the number of those k-mers
 // (included at the end of graph_extract.hip behind gfm_graph_variant.hpp, whose window list, layout enumeration and replay it
-// shares, and gfm_graph_hapaffinity.hpp, whose walk value it takes).
+// shares; it uses gfm_graph_table_score.hpp's window_sum, walk_value, walk_code and ConstraintAt).
 //
 // sums[slot] = (sum, rows), slot = site * 4 + allele (0 = none of the site's ALTs).  A walk of a window stands for the same
 // k-mer of carriers(walk) haplotypes -- the popcount over ALL bitset words of the AND of its constraints -- and qualifies for
@@ -70,20 +70,14 @@ graph_variant_affinity_kernel(GraphDev g, const unsigned *__restrict__ ftab, con
                 replay_walk<kVarMaxWalks>(g, p, W, i0, ws, st, q, prod, limit, em);
                 const int nc = em.n_cons;
                 if (nc == 0) continue;                      // a walk over no site: no allele's footprint
-                auto at = [&](int k, int &site, int &al) { const int v = em.get(k); site = v >> 4; al = v & 3; };
+                const ConstraintAt at{em};
                 unsigned long long carriers = 0ull;         // the FULL count: every word, not "some haplotype"
                 for (int word = 0; word < g.hw; ++word) carriers += (unsigned long long)__popcll(carrier_word<true>(g, nc, at, word));
                 if (carriers == 0ull) continue;             // a walk nobody carries adds nothing
-                unsigned sum = 0u;
-                int bad = 0;
-                for (int j = 0; j < W; ++j) {
-                    const unsigned c = base_code(src[j] >= 0 ? g.ref[src[j]] : km[j]);
-                    sum += ftab[j * 8 + (c & 7u)];
-                    bad |= (int)(c >> 2);
-                }
-                const unsigned long long value = ha_walk_value(wtab, sum, bad, min_val, forward_only);
+                const WindowSum w = window_sum(ftab, W, [&](int j) { return walk_code(g, src, km, j); });
+                const unsigned long long value = walk_value(wtab, w, min_val, forward_only);
                 // (the two strands' weights and the carriers' multiple are adds of the sum too: a wrap in them is one)
-                if (!forward_only && value < wtab[bad ? min_val : (int)(sum & 0xffffu)]) wrapped = 1;
+                if (!forward_only && value < wtab[strand_scores(w, min_val).plus]) wrapped = 1;
                 if (__umul64hi(carriers, value)) wrapped = 1;
                 const unsigned long long add = carriers * value, add_rows = carriers * strands;
                 for (int k = 0; k < nc; ++k) {
@@ -143,38 +137,23 @@ GFM_API int gfm_graph_variant_affinity(gfm_graph_t g, const gfm_motif_t *motifs,
     if (flags & ~(uint32_t)GFM_GRAPH_FORWARD_ONLY) return gfail(GFM_ERR_INVALID, "unknown flag");
     if (table_entries < 0 || table_entries > kVaTable || (table_entries & (table_entries - 1)))
         return gfail(GFM_ERR_INVALID, "table_entries: 0 or a power of two up to " + std::to_string(kVaTable));
-    int W = 0, mdev = -1;
-    std::vector<const unsigned *> ftab(n_motifs);
-    std::vector<int> min_val(n_motifs);
-    for (int m = 0; m < n_motifs; ++m) {
+    for (int m = 0; m < n_motifs; ++m)
         if (!motifs[m] || !d_weights[m] || !d_sums[m]) return gfail(GFM_ERR_INVALID, "NULL motif / device buffer");
-        const int64_t *sm = nullptr;
-        int Wm = 0, L = 0, lo = 0, nb = 0, dev_m = 0, n_cu = 0;
-        const int rc = gfm_motif_view_(motifs[m], kFusedMaxBins[0], 0, &sm, &Wm, &min_val[m], &L, &lo, &nb, &dev_m, &n_cu, &ftab[m]);
-        if (rc) return rc;
-        if (m == 0) { W = Wm; mdev = dev_m; }
-        else if (Wm != W || dev_m != mdev) return gfail(GFM_ERR_INVALID, "the motifs of one call have one width and live on one device");
-        if (min_val[m] < 0 || min_val[m] >= L || L > 65536) return gfail(GFM_ERR_INVALID, "scores outside the packed table's 16 bits");
-    }
-    for (int r = 0; r < n_regions; ++r)
-        if (h_stops[r] < h_starts[r]) return gfail(GFM_ERR_INVALID, "a region ends before it starts");
-    {
-        int dev = -1;
-        GX_TRY(hipGetDevice(&dev));
-        if (dev != mdev) return gfail(GFM_ERR_INVALID, "the motif lives on another device than the current one");
-    }
+    MotifSet ms;
+    if (const int rc = view_motif_set(motifs, n_motifs, ScoreBits::PackedTable, ms)) return rc;
+    if (const int rc = check_regions(n_regions, h_starts, h_stops)) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (const int rc = g->serialise(st)) return rc;
     long long n_win = 0;
-    if (const int rc = variant_stage_windows(g, W, n_regions, h_starts, h_stops, true, st, &n_win)) return rc;
+    if (const int rc = variant_stage_windows(g, ms.W, n_regions, h_starts, h_stops, true, st, &n_win)) return rc;
     if (n_windows) *n_windows = n_win;
     if (n_win > 0) {
         const int grid = (int)std::min<long long>(n_win, 1 << 16);
         const int fwd = (flags & GFM_GRAPH_FORWARD_ONLY) ? 1 : 0, table = table_entries ? table_entries : kVaTable;
         const VarWin *wins = static_cast<const VarWin *>(g->v_wins);
         for (int m = 0; m < n_motifs; ++m) {
-            hipLaunchKernelGGL(graph_variant_affinity_kernel, dim3(grid), dim3(kVaThreads), 0, st, g->dev, ftab[m],
-                               reinterpret_cast<const unsigned long long *>(d_weights[m]), W, min_val[m], wins, n_win, fwd, table,
+            hipLaunchKernelGGL(graph_variant_affinity_kernel, dim3(grid), dim3(kVaThreads), 0, st, g->dev, ms.ftab[m],
+                               reinterpret_cast<const unsigned long long *>(d_weights[m]), ms.W, ms.min_val[m], wins, n_win, fwd, table,
                                reinterpret_cast<unsigned long long *>(d_sums[m]), d_overflow);
             GX_TRY(hipGetLastError());
         }

@@ -180,6 +180,27 @@ __device__ __forceinline__ long long wave_sum_ll(long long v)
     }
     return v;
 }
+// the maximum over the wavefront's 64 lanes, in every lane
+__device__ __forceinline__ int wave_max(int v)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v = max(v, __shfl_xor(v, off));
+    return v;
+}
+// the 64-bit value of lane `r` (wave-uniform) in every lane
+__device__ __forceinline__ unsigned long long wave_readlane_ll(unsigned long long v, int r)
+{
+    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, r);
+    const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(v >> 32), r);
+    return ((unsigned long long)hi << 32) | lo;
+}
+// what the lanes wrote to LDS that only their own wavefront uses is read by other lanes of the wave (and the other way round)
+__device__ __forceinline__ void wave_lds_sync()
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
 
 // A walk may start inside an insertion anchored at p - 1 (start coordinate p): `pre_site` = that site (or -1),
 // `pre_t` = offset of its first base inside the inserted string.  next_start() steps through the starts of
@@ -1897,6 +1918,69 @@ constexpr int kFusedMaxBins[kMaxMM] = {16384, 8000, 5400};
 constexpr int kFusedSmallBins[kMaxMM] = {GFM_GRAPH_SMALL_BINS1, 6000, 5000};
 constexpr size_t kCuLdsBytes = 160 * 1024;
 
+// The motifs of one call of a table entry (the gfm_graph_*.hpp headers at the end of this file), viewed with the widest
+// single-motif bin window: one width, one device -- the current one --, per motif the packed two-strand table and min_val.
+struct MotifSet {
+    int W = 0, device = -1;
+    std::vector<const unsigned *> ftab;
+    std::vector<int> min_val;
+};
+// which 16 bits a motif's scaled scores [0, L) must fit: a 64-bit key's score field, or the halves of the packed table's
+// words, from which min_val is looked up as a score as well
+enum class ScoreBits { Key, PackedTable };
+
+int view_motif_set(const gfm_motif_t *motifs, int n_motifs, ScoreBits bits, MotifSet &ms)
+{
+    ms.ftab.resize((size_t)n_motifs);
+    ms.min_val.resize((size_t)n_motifs);
+    for (int m = 0; m < n_motifs; ++m) {
+        const int64_t *sm = nullptr;
+        int Wm = 0, L = 0, lo = 0, nb = 0, dev_m = 0, n_cu = 0;
+        const int rc = gfm_motif_view_(motifs[m], kFusedMaxBins[0], 0, &sm, &Wm, &ms.min_val[(size_t)m], &L, &lo, &nb, &dev_m, &n_cu,
+                                       &ms.ftab[(size_t)m]);
+        if (rc) return rc;
+        if (m == 0) { ms.W = Wm; ms.device = dev_m; }
+        else if (Wm != ms.W || dev_m != ms.device)
+            return gfail(GFM_ERR_INVALID, "the motifs of one call have one width and live on one device");
+        const int mv = ms.min_val[(size_t)m];
+        if (bits == ScoreBits::Key && (mv < 0 || L > 65536)) return gfail(GFM_ERR_INVALID, "scores outside the key's 16 bits");
+        if (bits == ScoreBits::PackedTable && (mv < 0 || mv >= L || L > 65536))
+            return gfail(GFM_ERR_INVALID, "scores outside the packed table's 16 bits");
+    }
+    if (ms.W < 1 || ms.W > GFM_MAX_WIDTH) return gfail(GFM_ERR_INVALID, "width outside [1, 64]");
+    int dev = -1;
+    GX_TRY(hipGetDevice(&dev));
+    if (dev != ms.device) return gfail(GFM_ERR_INVALID, "the motif lives on another device than the current one");
+    return GFM_OK;
+}
+
+// The motifs of one launch of a sequence table's kernel (grid.y = motif): per motif the packed table, the weight table and
+// min_val; the kernel's own output pointers travel beside it.  seq_motifs(): those of motifs m0 .. m0 + mm - 1 of a call.
+constexpr int kSeqMotifs = 16;
+struct SeqMotifs {
+    const unsigned *ftab[kSeqMotifs];
+    const unsigned long long *wtab[kSeqMotifs];
+    int min_val[kSeqMotifs];
+};
+SeqMotifs seq_motifs(const MotifSet &ms, const uint64_t *const *d_weights, int m0, int mm)
+{
+    SeqMotifs mt = {};
+    for (int k = 0; k < mm; ++k) {
+        mt.ftab[k] = ms.ftab[(size_t)(m0 + k)];
+        mt.wtab[k] = reinterpret_cast<const unsigned long long *>(d_weights[m0 + k]);
+        mt.min_val[k] = ms.min_val[(size_t)(m0 + k)];
+    }
+    return mt;
+}
+
+// the caller's region list: a region may be empty, or reach beyond the reference, but not end before it starts
+int check_regions(int n_regions, const int64_t *h_starts, const int64_t *h_stops)
+{
+    for (int r = 0; r < n_regions; ++r)
+        if (h_stops[r] < h_starts[r]) return gfail(GFM_ERR_INVALID, "a region ends before it starts");
+    return GFM_OK;
+}
+
 // first site at or behind `target`, searched from a hint (tiles come in ascending order: a step or two)
 int site_lower_bound(const std::vector<int> &pos, int hint, long long target)
 {
@@ -2550,6 +2634,7 @@ inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 }  // namespace
 
+#include "gfm_graph_table_score.hpp"
 #include "gfm_graph_variant.hpp"
 #include "gfm_graph_haplotypes.hpp"
 #include "gfm_graph_hapscores.hpp"
