@@ -112,7 +112,7 @@ def get_parser():
                         "haplotype's total binding affinity -- the sum of 2^(log-odds / T) over every k-mer of its own "
                         "sequence --, beside the reference's (graph routes only)")
     p.add_argument("--affinity-temperature", dest="affinity_temperature", type=float, default=None, metavar="T",
-                   help="with --haplotype-affinity, --variant-affinity, --haplotype-classes, --query-variants or --mutation-scan: the temperature T > 0 the log-odds scores are "
+                   help="with --haplotype-affinity, --variant-affinity, --haplotype-classes, --query-variants, --mutation-scan or --indel-scan: the temperature T > 0 the log-odds scores are "
                         "divided by; default 1")
     p.add_argument("--variant-affinity", action="store_true", dest="variant_affinity",
                    help="also write grafimo_variant_affinity[_MOTIF].tsv (printed with -f): per variant, the log2 of the mean "
@@ -124,7 +124,7 @@ def get_parser():
                    help="also write grafimo_hit_alleles[_MOTIF].tsv (printed with -f): the report's rows, each with the variant "
                         "alleles that make its k-mer and, with --haplotype-groups, its carriers per group (graph routes only)")
     p.add_argument("--haplotype-groups", dest="haplotype_groups", metavar="FILE",
-                   help="with --hit-alleles, --hit-pairs, --haplotype-classes, --haplotype-sequences, --query-variants or --mutation-scan: SAMPLE GROUP lines (the 1000 Genomes panel file reads as is), one "
+                   help="with --hit-alleles, --hit-pairs, --haplotype-classes, --haplotype-sequences, --query-variants, --mutation-scan or --indel-scan: SAMPLE GROUP lines (the 1000 Genomes panel file reads as is), one "
                         "haplotypes_GROUP column per group")
     p.add_argument("--haplotype-classes", action="store_true", dest="haplotype_classes",
                    help="also write grafimo_haplotype_classes[_MOTIF].tsv (printed with -f) and "
@@ -158,6 +158,18 @@ def get_parser():
                    help="with --mutation-scan: also keep the rows with |delta_log2_affinity| >= X")
     p.add_argument("--mutation-all", action="store_true", dest="mutation_all",
                    help="with --mutation-scan: keep every row, three per base")
+    p.add_argument("--indel-scan", action="store_true", dest="indel_scan",
+                   help="also write grafimo_indel_scan[_MOTIF].tsv and grafimo_indel_scan_summary[_MOTIF].tsv (printed with "
+                        "-f): the mutation scan's companion for one-base indels -- the deletion of every base and the insertion "
+                        "of A, C, G and T behind every base of every sequence the haplotypes spell in a region (inserted "
+                        "bases too) and of the reference sequence, with the best hit and the total affinity "
+                        "(--affinity-temperature) before and after, gain / loss on p < -t and its haplotypes, also per "
+                        "--haplotype-groups group; rows are kept on gain or loss; in a homopolymer a change is reported "
+                        "once, at its leftmost offset (graph routes only)")
+    p.add_argument("--indel-delta", dest="indel_delta", type=float, default=None, metavar="X",
+                   help="with --indel-scan: also keep the rows with |delta_log2_affinity| >= X")
+    p.add_argument("--indel-all", action="store_true", dest="indel_all",
+                   help="with --indel-scan: keep every row, up to five per base")
     p.add_argument("--hit-pairs", action="store_true", dest="hit_pairs",
                    help="also write grafimo_hit_pairs.tsv (printed with -f): the pairs of report rows -- of one motif or of "
                         "two -- of a region that lie within --pair-gap of each other and share carrier haplotypes, with how "
@@ -236,7 +248,8 @@ _GRAPH_TABLES = {"variant_effects": ("--variant-effects", "alleles"), "haplotype
                  "hit_pairs": ("--hit-pairs", "walks"), "hit_linkage": ("--hit-linkage", "walks"),
                  "haplotype_classes": ("--haplotype-classes", "haplotypes"),
                  "haplotype_sequences": ("--haplotype-sequences", "haplotypes"),
-                 "query_variants": ("--query-variants", "haplotypes"), "mutation_scan": ("--mutation-scan", "haplotypes")}
+                 "query_variants": ("--query-variants", "haplotypes"), "mutation_scan": ("--mutation-scan", "haplotypes"),
+                 "indel_scan": ("--indel-scan", "haplotypes")}
 
 
 def _graph_only(a, table):
@@ -275,7 +288,7 @@ def main(argv=None):
     _graph_only(a, "haplotype_hits")
     _graph_only(a, "haplotype_scores")
     if a.affinity_temperature is not None and not (a.haplotype_affinity or a.variant_affinity or a.haplotype_classes
-                                                    or a.query_variants or a.mutation_scan):
+                                                    or a.query_variants or a.mutation_scan or a.indel_scan):
         sys.exit("ERROR: --affinity-temperature goes with --haplotype-affinity or --variant-affinity or --haplotype-classes")
     if a.affinity_temperature is not None and not a.affinity_temperature > 0:
         sys.exit(f"ERROR: --affinity-temperature {a.affinity_temperature} is not > 0")
@@ -286,7 +299,7 @@ def main(argv=None):
         sys.exit(f"ERROR: --variant-affinity-delta {a.variant_affinity_delta} is not >= 0")
     _graph_only(a, "variant_affinity")
     if a.haplotype_groups and not (a.hit_alleles or a.hit_pairs or a.haplotype_classes or a.haplotype_sequences
-                                   or a.query_variants or a.mutation_scan):
+                                   or a.query_variants or a.mutation_scan or a.indel_scan):
         sys.exit("ERROR: --haplotype-groups goes with --hit-alleles or --hit-pairs or --haplotype-classes or "
                  "--haplotype-sequences")
     if a.class_min_haplotypes is not None and not a.haplotype_classes:
@@ -309,6 +322,13 @@ def main(argv=None):
     if a.mutation_delta is not None and not a.mutation_delta >= 0:
         sys.exit(f"ERROR: --mutation-delta {a.mutation_delta} is not >= 0")
     _graph_only(a, "mutation_scan")
+    if a.indel_all and not a.indel_scan:
+        sys.exit("ERROR: --indel-all goes with --indel-scan")
+    if a.indel_delta is not None and not a.indel_scan:
+        sys.exit("ERROR: --indel-delta goes with --indel-scan")
+    if a.indel_delta is not None and not a.indel_delta >= 0:
+        sys.exit(f"ERROR: --indel-delta {a.indel_delta} is not >= 0")
+    _graph_only(a, "indel_scan")
     if a.pair_gap is not None and not a.hit_pairs:
         sys.exit("ERROR: --pair-gap goes with --hit-pairs")
     if a.pair_gap is not None and a.pair_gap[0] > a.pair_gap[1]:
@@ -510,6 +530,17 @@ def main(argv=None):
             for motif, t in zip(motifs, tables):
                 print(f"{len(t.summary_frame())} mutation scan summary rows written to "
                       f"{write_mutation_scan_summary(t, motif, len(motifs), wf)}")
+    if a.indel_scan:
+        from .indel_scan import compute_indel_scan_many, print_indel_scan, write_indel_scan, write_indel_scan_summary
+        graph, regions, first_index = source("indel_scan")
+        tables = compute_indel_scan_many(motifs, graph, regions, a.debug, wf, haplotype_groups=groups(first_index),
+                                         temperature=1.0 if a.affinity_temperature is None else a.affinity_temperature,
+                                         delta=a.indel_delta, all_rows=a.indel_all)
+        emit(tables, write_indel_scan, print_indel_scan, lambda t: f"{len(t)} indel scan rows")
+        if not a.text_only:
+            for motif, t in zip(motifs, tables):
+                print(f"{len(t.summary_frame())} indel scan summary rows written to "
+                      f"{write_indel_scan_summary(t, motif, len(motifs), wf)}")
     if sequences_loc:
         import shutil
         shutil.rmtree(sequences_loc, ignore_errors=True)

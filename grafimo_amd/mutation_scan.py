@@ -53,24 +53,26 @@ for _k, _c in enumerate(b"ACGT"):
 
 
 # ---------------------------------------------------------------------------------------------------------------- the kernel
-def _stage(tables, seq_offsets: np.ndarray, bases: np.ndarray):
+def _stage(tables, seq_offsets: np.ndarray, bases: np.ndarray, columns: int = 5):
     """the inputs of gfm_sequence_mutation_scan on the current device and its result tensors -> (seq_offsets (host), the bases'
-    tensor, the weight tables' tensors, the largest weight, keys int32 [M, N, 5], sums int64 [M, N, 5], the status word)"""
+    tensor, the weight tables' tensors, the largest weight, keys int32 [M, N, 5], sums int64 [M, N, 5], the status word).
+    `columns`: of an entry with the same arguments and another number of columns (indel_scan's 7)"""
     torch = _torch()
     M, N = len(tables), int(seq_offsets[-1])
     dev = torch.device("cuda", torch.cuda.current_device())
     d_bases = torch.from_numpy(np.array(bases, dtype=np.uint8)).to(dev)             # (a copy: the caller's may be read-only)
     d_tabs = [torch.from_numpy(np.ascontiguousarray(t, dtype=np.uint64).view(np.int64)).to(dev) for t in tables]
-    return (seq_offsets, d_bases, d_tabs, max(int(t.max()) for t in tables), torch.empty((M, N, 5), dtype=torch.int32, device=dev),
-            torch.empty((M, N, 5), dtype=torch.int64, device=dev), torch.zeros(1, dtype=torch.int32, device=dev))
+    return (seq_offsets, d_bases, d_tabs, max(int(t.max()) for t in tables), torch.empty((M, N, columns), dtype=torch.int32, device=dev),
+            torch.empty((M, N, columns), dtype=torch.int64, device=dev), torch.zeros(1, dtype=torch.int32, device=dev))
 
 
-def _enqueue(dms, staged, forward_only: bool):
-    """gfm_sequence_mutation_scan over staged inputs (_stage): every row of the result tensors is written -> (keys, sums)"""
+def _enqueue(dms, staged, forward_only: bool, entry: str = "gfm_sequence_mutation_scan"):
+    """gfm_sequence_mutation_scan (or `entry`, which takes the same arguments) over staged inputs (_stage): every row of the
+    result tensors is written -> (keys, sums)"""
     seq_offsets, d_bases, d_tabs, max_weight, keys, sums, status = staged
     M = len(dms)
     vp = ctypes.c_void_p
-    nv.check(nv.lib().gfm_sequence_mutation_scan(
+    nv.check(getattr(nv.lib(), entry)(
         (vp * M)(*[x.handle for x in dms]), M, (vp * M)(*[t.data_ptr() for t in d_tabs]), max_weight, len(seq_offsets) - 1,
         seq_offsets.ctypes.data, d_bases.data_ptr(), nv.GFM_GRAPH_FORWARD_ONLY if forward_only else 0,
         (vp * M)(*[keys[m].data_ptr() for m in range(M)]), (vp * M)(*[sums[m].data_ptr() for m in range(M)]),
@@ -78,12 +80,13 @@ def _enqueue(dms, staged, forward_only: bool):
     return keys, sums
 
 
-def _scan(dms, tables, seq_offsets: np.ndarray, bases: np.ndarray, forward_only: bool):
+def _scan(dms, tables, seq_offsets: np.ndarray, bases: np.ndarray, forward_only: bool, entry: str = "gfm_sequence_mutation_scan",
+          columns: int = 5):
     """gfm_sequence_mutation_scan for leased motifs of one width -> (keys uint32 [M, N, 5], sums uint64 [M, N, 5])"""
     M = len(dms)
     if int(seq_offsets[-1]) == 0:
-        return np.zeros((M, 0, 5), dtype=np.uint32), np.zeros((M, 0, 5), dtype=np.uint64)
-    keys, sums = _enqueue(dms, _stage(tables, seq_offsets, bases), forward_only)
+        return np.zeros((M, 0, columns), dtype=np.uint32), np.zeros((M, 0, columns), dtype=np.uint64)
+    keys, sums = _enqueue(dms, _stage(tables, seq_offsets, bases, columns), forward_only, entry)
     return keys.cpu().numpy().view(np.uint32), sums.cpu().numpy().view(np.uint64)
 
 
@@ -97,13 +100,14 @@ def _checked_sequences(seq_offsets, bases) -> Tuple[np.ndarray, np.ndarray]:
     return seq_offsets, bases
 
 
-def _scan_chunked(motifs: Sequence, seq_offsets, bases, weights, temperature, forward_only, max_bytes):
+def _scan_chunked(motifs: Sequence, seq_offsets, bases, weights, temperature, forward_only, max_bytes,
+                  entry: str = "gfm_sequence_mutation_scan", columns: int = 5):
     """-> (per motif (keys, sums), per motif its log2 offset, per motif (scale, offset, ptable)): the motifs leased and scanned
     in chunks whose result tensors stay under max_bytes"""
     from .device import DeviceMotif
     if weights is not None and len(weights) != len(motifs):
         raise ValueError(f"{len(weights)} weight tables for {len(motifs)} motifs")
-    per_motif = BYTES_PER_BASE * int(seq_offsets[-1])
+    per_motif = columns * (4 + 8) * int(seq_offsets[-1])
     if per_motif > int(max_bytes):
         raise ValueError(f"{motifs[0].motif_id}: the keys and sums of one motif over {int(seq_offsets[-1])} bases hold {per_motif} "
                          f"bytes, more than max_bytes = {int(max_bytes)}: scan fewer sequences at a time, or raise max_bytes")
@@ -114,7 +118,7 @@ def _scan_chunked(motifs: Sequence, seq_offsets, bases, weights, temperature, fo
         dms = [DeviceMotif.lease(m) for m in chunk]
         try:
             tables, offs = _weight_tables(dms, chunk, None if weights is None else list(weights[m0:m0 + step]), temperature)
-            keys, sums = _scan(dms, tables, seq_offsets, bases, forward_only)
+            keys, sums = _scan(dms, tables, seq_offsets, bases, forward_only, entry, columns)
             results += [(keys[m], sums[m]) for m in range(len(chunk))]
             offsets += offs
             numbers += [(dm.scale, dm.offset, dm.ptable_host()) for dm in dms]

@@ -892,6 +892,39 @@ int gfm_sequence_mutation_scan(const gfm_motif_t *motifs, int32_t n_motifs, cons
                                int32_t n_seqs, const int64_t *seq_offsets, const uint8_t *d_bases, uint32_t flags,
                                uint32_t *const *d_keys, uint64_t *const *d_sums, int32_t *d_status, void *stream);
 
+/* ------------------------------------------------------------------ indel scan: every one-base deletion and insertion of a spelled sequence
+ * Graph-independent.  THE RULE.  For a sequence x of n bases, a motif of width W, and every offset o in 0 .. n - 1:
+ *   Deletion of x[o].  y = x[:o] + x[o+1:].  This is gfm_graph_query_edits' rule with lr = 1, la = 0 at offset o.
+ *     REF side (column COVER): the starts s of x with max(0, o - W + 1) <= s <= min(o, n - W).  This is exactly the mutation
+ *     scan's REF column.
+ *     ALT side (column DEL): the starts of y across the junction, max(0, o - W + 1) <= s <= min(o - 1, n - 1 - W).
+ *   Insertion of b in A, C, G, T behind x[o].  y = x[:o+1] + b + x[o+1:].  This is the query rule with lr = 0, la = 1 at offset
+ *   o' = o + 1.
+ *     REF side (column JUNCTION): the starts of x across the junction, max(0, o' - W + 1) <= s <= min(o' - 1, n - W).
+ *     ALT side (columns INS_A, INS_C, INS_G, INS_T): the starts of y with max(0, o' - W + 1) <= s <= min(o', n + 1 - W).
+ *   Every window is scored once per strand, or + only under GFM_GRAPH_FORWARD_ONLY.
+ *   A window that holds a base that is not A/C/G/T scores min_val on both strands.  Case is folded, as base_code does.
+ *   Per column, the best window by (score descending, s ascending, + before -), as the key
+ *   ((score + 1) << 8) | ((64 - rel) << 1) | plus, rel = s - o for COVER and DEL, rel = s - (o + 1) for JUNCTION and INS_*: the
+ *   values a gfm_edit_record_t of the same edit holds.  Key 0 means the side has no window.
+ *   Per column, the exact uint64 sum of w[score] over the side's windows and strands.
+ *   A deleted N can repair its windows.  An N elsewhere leaves its windows at min_val.  An insertion before the first base of a
+ *   sequence is not scanned: every row has the base it is anchored to, as a VCF row has.  An empty sequence has no rows.
+ * By construction the columns equal, field for field, what gfm_graph_query_edits returns for the deletion (coordinate of o,
+ * x[o], "") and the insertion (coordinate of o + 1, "", b) applied to x, wherever a coordinate can name the edit.
+ *
+ * The arguments, the refusals and the wait are gfm_sequence_mutation_scan's: motifs of ONE width, d_weights and max_weight
+ * (refused when max_weight * 2 * W passes 2^64 - 1: a side has at most W windows), seq_offsets on the HOST, ascending from
+ * seq_offsets[0] >= 0, no sequence of 2^31 bases or more.  d_keys[m] uint32 [seq_offsets[n_seqs]][7] and d_sums[m] uint64
+ * [seq_offsets[n_seqs]][7]: per base of d_bases the columns COVER, DEL, JUNCTION, INS_A, INS_C, INS_G, INS_T.  Every row of a
+ * sequence is written, nothing is zeroed by the caller.  The work is cut into (sequence, GFM_INDELSCAN_TILE offsets) tiles by
+ * the library; the result does not depend on the tile -- it is exported only so that tests can aim at its edges.  No sequence
+ * or no base returns GFM_OK and touches nothing.  The call WAITS for the stream. */
+#define GFM_INDELSCAN_TILE 64
+int gfm_sequence_indel_scan(const gfm_motif_t *motifs, int32_t n_motifs, const uint64_t *const *d_weights, uint64_t max_weight,
+                            int32_t n_seqs, const int64_t *seq_offsets, const uint8_t *d_bases, uint32_t flags,
+                            uint32_t *const *d_keys, uint64_t *const *d_sums, int32_t *d_status, void *stream);
+
 /* ------------------------------------------------------------------ hit pairs: rows close to each other that share carriers
  * Graph-independent (csrc/hit_pairs.hip).  n rows (n < 2^31 - 1) in device memory, in ascending (d_group, d_lo) order:
  * d_group int32, d_lo <= d_hi int64 (|x| < 2^61), d_masks uint64 [n][hw] (hw >= 1 words of a bitset whose unused tail
