@@ -112,7 +112,7 @@ def get_parser():
                         "haplotype's total binding affinity -- the sum of 2^(log-odds / T) over every k-mer of its own "
                         "sequence --, beside the reference's (graph routes only)")
     p.add_argument("--affinity-temperature", dest="affinity_temperature", type=float, default=None, metavar="T",
-                   help="with --haplotype-affinity, --variant-affinity, --haplotype-classes, --query-variants, --mutation-scan or --indel-scan: the temperature T > 0 the log-odds scores are "
+                   help="with --haplotype-affinity, --variant-affinity, --haplotype-classes, --query-variants, --mutation-scan, --indel-scan or --shuffle-null: the temperature T > 0 the log-odds scores are "
                         "divided by; default 1")
     p.add_argument("--variant-affinity", action="store_true", dest="variant_affinity",
                    help="also write grafimo_variant_affinity[_MOTIF].tsv (printed with -f): per variant, the log2 of the mean "
@@ -124,7 +124,7 @@ def get_parser():
                    help="also write grafimo_hit_alleles[_MOTIF].tsv (printed with -f): the report's rows, each with the variant "
                         "alleles that make its k-mer and, with --haplotype-groups, its carriers per group (graph routes only)")
     p.add_argument("--haplotype-groups", dest="haplotype_groups", metavar="FILE",
-                   help="with --hit-alleles, --hit-pairs, --haplotype-classes, --haplotype-sequences, --query-variants, --mutation-scan or --indel-scan: SAMPLE GROUP lines (the 1000 Genomes panel file reads as is), one "
+                   help="with --hit-alleles, --hit-pairs, --haplotype-classes, --haplotype-sequences, --query-variants, --mutation-scan, --indel-scan or --shuffle-null: SAMPLE GROUP lines (the 1000 Genomes panel file reads as is), one "
                         "haplotypes_GROUP column per group")
     p.add_argument("--haplotype-classes", action="store_true", dest="haplotype_classes",
                    help="also write grafimo_haplotype_classes[_MOTIF].tsv (printed with -f) and "
@@ -170,6 +170,15 @@ def get_parser():
                    help="with --indel-scan: also keep the rows with |delta_log2_affinity| >= X")
     p.add_argument("--indel-all", action="store_true", dest="indel_all",
                    help="with --indel-scan: keep every row, up to five per base")
+    p.add_argument("--shuffle-null", dest="shuffle_null", nargs="?", type=int, const=1000, default=None, metavar="K",
+                   help="also write grafimo_shuffle_null[_MOTIF].tsv and grafimo_motif_enrichment.tsv (printed with -f): every "
+                        "sequence the haplotypes spell in a region, and the reference sequence, against K (default 1000) "
+                        "composition-preserving shuffles of itself -- the empirical p-values (1 + ge) / (K + 1) of its best "
+                        "score and of its total affinity (--affinity-temperature), with its haplotypes, also per "
+                        "--haplotype-groups group --, and per motif how many regions hold a hit at p < -t against the same "
+                        "count over the shuffles (graph routes only)")
+    p.add_argument("--null-seed", dest="null_seed", type=int, default=None, metavar="N",
+                   help="with --shuffle-null: the seed of the shuffles, 0 .. 2^64 - 1; default 0")
     p.add_argument("--hit-pairs", action="store_true", dest="hit_pairs",
                    help="also write grafimo_hit_pairs.tsv (printed with -f): the pairs of report rows -- of one motif or of "
                         "two -- of a region that lie within --pair-gap of each other and share carrier haplotypes, with how "
@@ -249,7 +258,7 @@ _GRAPH_TABLES = {"variant_effects": ("--variant-effects", "alleles"), "haplotype
                  "haplotype_classes": ("--haplotype-classes", "haplotypes"),
                  "haplotype_sequences": ("--haplotype-sequences", "haplotypes"),
                  "query_variants": ("--query-variants", "haplotypes"), "mutation_scan": ("--mutation-scan", "haplotypes"),
-                 "indel_scan": ("--indel-scan", "haplotypes")}
+                 "indel_scan": ("--indel-scan", "haplotypes"), "shuffle_null": ("--shuffle-null", "haplotypes")}
 
 
 def _graph_only(a, table):
@@ -288,7 +297,7 @@ def main(argv=None):
     _graph_only(a, "haplotype_hits")
     _graph_only(a, "haplotype_scores")
     if a.affinity_temperature is not None and not (a.haplotype_affinity or a.variant_affinity or a.haplotype_classes
-                                                    or a.query_variants or a.mutation_scan or a.indel_scan):
+                                                    or a.query_variants or a.mutation_scan or a.indel_scan or a.shuffle_null):
         sys.exit("ERROR: --affinity-temperature goes with --haplotype-affinity or --variant-affinity or --haplotype-classes")
     if a.affinity_temperature is not None and not a.affinity_temperature > 0:
         sys.exit(f"ERROR: --affinity-temperature {a.affinity_temperature} is not > 0")
@@ -299,7 +308,7 @@ def main(argv=None):
         sys.exit(f"ERROR: --variant-affinity-delta {a.variant_affinity_delta} is not >= 0")
     _graph_only(a, "variant_affinity")
     if a.haplotype_groups and not (a.hit_alleles or a.hit_pairs or a.haplotype_classes or a.haplotype_sequences
-                                   or a.query_variants or a.mutation_scan or a.indel_scan):
+                                   or a.query_variants or a.mutation_scan or a.indel_scan or a.shuffle_null):
         sys.exit("ERROR: --haplotype-groups goes with --hit-alleles or --hit-pairs or --haplotype-classes or "
                  "--haplotype-sequences")
     if a.class_min_haplotypes is not None and not a.haplotype_classes:
@@ -329,6 +338,13 @@ def main(argv=None):
     if a.indel_delta is not None and not a.indel_delta >= 0:
         sys.exit(f"ERROR: --indel-delta {a.indel_delta} is not >= 0")
     _graph_only(a, "indel_scan")
+    if a.null_seed is not None and a.shuffle_null is None:
+        sys.exit("ERROR: --null-seed goes with --shuffle-null")
+    if a.null_seed is not None and not 0 <= a.null_seed < 2**64:
+        sys.exit(f"ERROR: --null-seed {a.null_seed} outside [0, 2^64 - 1]")
+    if a.shuffle_null is not None and not 1 <= a.shuffle_null <= 2**20:
+        sys.exit(f"ERROR: --shuffle-null {a.shuffle_null} outside [1, 2^20]")
+    _graph_only(a, "shuffle_null")
     if a.pair_gap is not None and not a.hit_pairs:
         sys.exit("ERROR: --pair-gap goes with --hit-pairs")
     if a.pair_gap is not None and a.pair_gap[0] > a.pair_gap[1]:
@@ -541,6 +557,18 @@ def main(argv=None):
             for motif, t in zip(motifs, tables):
                 print(f"{len(t.summary_frame())} indel scan summary rows written to "
                       f"{write_indel_scan_summary(t, motif, len(motifs), wf)}")
+    if a.shuffle_null is not None:                     # (a table per motif, and one row per motif for the whole call)
+        from .shuffle_null import (compute_shuffle_null_many, print_motif_enrichment, print_shuffle_null, write_motif_enrichment,
+                                   write_shuffle_null)
+        graph, regions, first_index = source("shuffle_null")
+        tables = compute_shuffle_null_many(motifs, graph, regions, a.debug, wf, haplotype_groups=groups(first_index),
+                                           temperature=1.0 if a.affinity_temperature is None else a.affinity_temperature,
+                                           replicates=a.shuffle_null, seed=a.null_seed or 0)
+        emit(tables, write_shuffle_null, print_shuffle_null, lambda t: f"{len(t)} shuffle null rows")
+        if a.text_only:
+            print_motif_enrichment(tables)
+        else:
+            print(f"{len(tables)} motif enrichment rows written to {write_motif_enrichment(tables, wf)}")
     if sequences_loc:
         import shutil
         shutil.rmtree(sequences_loc, ignore_errors=True)

@@ -42,6 +42,8 @@ GFM_QUERY_MAX_ALLELE = 64
 GFM_EDIT_APPLIED, GFM_EDIT_ABSENT, GFM_EDIT_MISMATCH, GFM_EDIT_INVALID = 0, 1, 2, 3
 GFM_MUTSCAN_TILE = 64          # (the library's own decomposition: exported for tests that aim at a tile's edges)
 GFM_INDELSCAN_TILE = 64        # (as GFM_MUTSCAN_TILE)
+GFM_NULL_LDS_BASES = 960       # (the shuffle null's longest sequence shuffled in the LDS: exported for tests that aim at its edge)
+GFM_NULL_MAX_REPLICATES = 1 << 20
 ABI_VERSION = 12
 RANGE = 1000
 
@@ -169,6 +171,9 @@ PROTOTYPES = {
                                            c_void_p, c_void_p, c_void_p]),
     "gfm_sequence_indel_scan": (c_int, [c_void_p, c_i32, c_void_p, c_u64, c_i32, c_void_p, c_void_p, ctypes.c_uint32, c_void_p,
                                         c_void_p, c_void_p, c_void_p]),
+    "gfm_sequence_shuffle_null": (c_int, [c_void_p, c_i32, c_void_p, c_u64, c_i32, c_void_p, c_void_p, c_void_p, c_void_p, c_i32,
+                                          c_u64, c_void_p, ctypes.c_uint32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                          c_void_p, c_void_p, c_void_p, c_void_p]),
     "gfm_hit_pairs": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_i32, c_i64, c_i64, c_i32, c_void_p, c_void_p, c_i64,
                               c_void_p, c_void_p, c_void_p, ctypes.c_uint32, P(c_i64), c_void_p]),
     "gfm_hit_linkage": (c_int, [c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_i64, c_i32, c_i32, c_i64,

@@ -23,6 +23,7 @@ The hot path is HIP (grafimo_amd/csrc/gfm_graph_mutation_scan.hpp, gfm_sequence_
 scored once, the 4 n changes are derived from the stored sums.  Everything from the kernel's arrays to the frames is numpy
 group-bys; there is no Python step per row or per base.
 """
+import contextlib
 import ctypes
 import sys
 from typing import List, Mapping, Optional, Sequence, Tuple
@@ -100,11 +101,28 @@ def _checked_sequences(seq_offsets, bases) -> Tuple[np.ndarray, np.ndarray]:
     return seq_offsets, bases
 
 
+def _leased_chunks(motifs: Sequence, weights, temperature, step: int):
+    """The motifs `step` at a time, leased for as long as the caller holds the item -> (m0, the leased handles, their weight
+    tables, their log2 offsets, per motif (scale, offset, ptable)) per chunk; the handles are given back when the caller asks
+    for the next chunk, or fails.  What the sequence tables' chunked calls share (_scan_chunked, shuffle_null)."""
+    from .device import DeviceMotif
+    if weights is not None and len(weights) != len(motifs):
+        raise ValueError(f"{len(weights)} weight tables for {len(motifs)} motifs")
+    for m0 in range(0, len(motifs), step):
+        chunk = list(motifs[m0:m0 + step])
+        dms = [DeviceMotif.lease(m) for m in chunk]
+        try:
+            tables, offs = _weight_tables(dms, chunk, None if weights is None else list(weights[m0:m0 + step]), temperature)
+            yield m0, dms, tables, offs, [(dm.scale, dm.offset, dm.ptable_host()) for dm in dms]
+        finally:
+            for dm in dms:
+                dm.release()
+
+
 def _scan_chunked(motifs: Sequence, seq_offsets, bases, weights, temperature, forward_only, max_bytes,
                   entry: str = "gfm_sequence_mutation_scan", columns: int = 5):
     """-> (per motif (keys, sums), per motif its log2 offset, per motif (scale, offset, ptable)): the motifs leased and scanned
     in chunks whose result tensors stay under max_bytes"""
-    from .device import DeviceMotif
     if weights is not None and len(weights) != len(motifs):
         raise ValueError(f"{len(weights)} weight tables for {len(motifs)} motifs")
     per_motif = columns * (4 + 8) * int(seq_offsets[-1])
@@ -113,18 +131,12 @@ def _scan_chunked(motifs: Sequence, seq_offsets, bases, weights, temperature, fo
                          f"bytes, more than max_bytes = {int(max_bytes)}: scan fewer sequences at a time, or raise max_bytes")
     step = max(1, int(max_bytes) // max(per_motif, 1))
     results, offsets, numbers = [], [], []
-    for m0 in range(0, len(motifs), step):
-        chunk = list(motifs[m0:m0 + step])
-        dms = [DeviceMotif.lease(m) for m in chunk]
-        try:
-            tables, offs = _weight_tables(dms, chunk, None if weights is None else list(weights[m0:m0 + step]), temperature)
+    with contextlib.closing(_leased_chunks(motifs, weights, temperature, step)) as chunks:     # (a failure gives the handles back)
+        for _, dms, tables, offs, nums in chunks:
             keys, sums = _scan(dms, tables, seq_offsets, bases, forward_only, entry, columns)
-            results += [(keys[m], sums[m]) for m in range(len(chunk))]
+            results += [(keys[m], sums[m]) for m in range(len(dms))]
             offsets += offs
-            numbers += [(dm.scale, dm.offset, dm.ptable_host()) for dm in dms]
-        finally:
-            for dm in dms:
-                dm.release()
+            numbers += nums
     return results, offsets, numbers
 
 

@@ -925,6 +925,53 @@ int gfm_sequence_indel_scan(const gfm_motif_t *motifs, int32_t n_motifs, const u
                             int32_t n_seqs, const int64_t *seq_offsets, const uint8_t *d_bases, uint32_t flags,
                             uint32_t *const *d_keys, uint64_t *const *d_sums, int32_t *d_status, void *stream);
 
+/* ------------------------------------------------------------------ shuffle null: empirical p-values for best score and total affinity
+ * Graph-independent.  THE RULE.  All arithmetic on 64-bit words is modulo 2^64.
+ *   G = 0x9E3779B97F4A7C15.
+ *   mix(z): z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27; z *= 0x94D049BB133111EB; z ^= z >> 31.
+ * For a sequence x of n bases with the caller's uint64 key k, a uint64 seed and the replicates r = 0 .. K - 1:
+ *   s0 = mix(mix(seed + k G) + r).
+ *   y starts as a copy of x: the bytes as they are, non-ACGT and lower case included.
+ *   For i = n - 1 down to 1:  u = mix(s0 + i G);  j = ((u >> 32) (i + 1)) >> 32;  swap y[i] and y[j].
+ *   The multiply-shift bias is at most n / 2^32 and is part of the rule.  The permutation depends on (seed, k, r, n) only, not
+ *   on the motif or on anything else in the call.
+ * Scores, for a motif of width W:
+ *   Every window start 0 .. n - W of a sequence is scored once per strand, + only under GFM_GRAPH_FORWARD_ONLY.
+ *   A window that holds a base that is not A/C/G/T scores min_val on both strands.  Case is folded, as base_code does.
+ *   best = the largest score over windows and strands, -1 when n < W.
+ *   sum = the exact uint64 sum of w[score] over windows and strands, 0 when there are none.
+ *   obs_best, obs_sum: those of x itself.
+ * Per (motif, sequence): obs_best int32, obs_sum uint64, ge_best = #{r : best_r >= obs_best} and ge_sum = #{r : sum_r >= obs_sum},
+ * uint32.  Ties count, the conservative choice; n < W gives ge_best = ge_sum = K.
+ * Per (motif, replicate), when asked for: rep_hits[r] = the sum over the sequences v of seq_weight[v] [best_{v,r} >= cut[m]],
+ * uint64; cut[m] is a scaled score in [0, L] (L: no replicate reaches it).
+ * Per (motif, sequence, replicate), when asked for: the dense rep_best int32 [n_seqs][K] and rep_sum uint64 [n_seqs][K].
+ * The result for one sequence depends on (seed, its key, its bytes, K, the motif, the weights, the flag) only: not on its
+ * neighbours in the call, nor on how the library cuts the work.
+ *
+ * n_motifs motifs of ONE width on the current device, d_weights[m] uint64 [table length] per motif and max_weight, the largest
+ * weight of all tables (host): refused when max_weight * 2 * (longest n - W + 1) passes 2^64 - 1.  seq_offsets: HOST, int64
+ * [n_seqs + 1], ascending from seq_offsets[0] >= 0; empty sequences are allowed and have results like any other.  d_seq_keys
+ * uint64 [n_seqs]; d_seq_weight uint32 [n_seqs], NULL: every weight is 1.  n_replicates = K in [1, 2^20].  cuts: HOST, int32
+ * [n_motifs].  The arrays of pointers d_obs_best .. d_rep_sum hold a device pointer per motif: d_obs_best[m] int32 [n_seqs],
+ * d_obs_sum[m] uint64 [n_seqs], d_ge_best[m] and d_ge_sum[m] uint32 [n_seqs]; d_rep_hits[m] uint64 [K], d_rep_best[m] int32
+ * [n_seqs][K], d_rep_sum[m] uint64 [n_seqs][K], each of which may be NULL and is then not computed.  Every output that is given
+ * is overwritten, nothing is zeroed by the caller.  d_status int32: a device word of the caller's, cleared and read here.
+ * A sequence of up to GFM_NULL_LDS_BASES bases is shuffled in the LDS, a longer one in device memory the call allocates on the
+ * stream (64 bytes a base and workgroup: a sequence it cannot allocate for gives GFM_ERR_HIP); the result does not depend on
+ * which -- the constant is exported only so that tests can aim at its edge.
+ * No sequence returns GFM_OK and touches nothing.  GFM_ERR_INVALID: a NULL pointer, motifs of different widths or on another
+ * device than the current one, a width outside [1, 64], n_replicates outside [1, 2^20], a cut outside [0, L], weights that can
+ * overflow a sum, offsets that descend, a sequence of 2^31 bases or more, an unknown flag.  The call WAITS for the stream (it
+ * reads the verdict of the device's check of its sequence table). */
+#define GFM_NULL_LDS_BASES 960
+int gfm_sequence_shuffle_null(const gfm_motif_t *motifs, int32_t n_motifs, const uint64_t *const *d_weights, uint64_t max_weight,
+                              int32_t n_seqs, const int64_t *seq_offsets, const uint8_t *d_bases, const uint64_t *d_seq_keys,
+                              const uint32_t *d_seq_weight, int32_t n_replicates, uint64_t seed, const int32_t *cuts,
+                              uint32_t flags, int32_t *const *d_obs_best, uint64_t *const *d_obs_sum, uint32_t *const *d_ge_best,
+                              uint32_t *const *d_ge_sum, uint64_t *const *d_rep_hits, int32_t *const *d_rep_best,
+                              uint64_t *const *d_rep_sum, int32_t *d_status, void *stream);
+
 /* ------------------------------------------------------------------ hit pairs: rows close to each other that share carriers
  * Graph-independent (csrc/hit_pairs.hip).  n rows (n < 2^31 - 1) in device memory, in ascending (d_group, d_lo) order:
  * d_group int32, d_lo <= d_hi int64 (|x| < 2^61), d_masks uint64 [n][hw] (hw >= 1 words of a bitset whose unused tail
