@@ -179,6 +179,10 @@ def get_parser():
                         "count over the shuffles (graph routes only)")
     p.add_argument("--null-seed", dest="null_seed", type=int, default=None, metavar="N",
                    help="with --shuffle-null: the seed of the shuffles, 0 .. 2^64 - 1; default 0")
+    p.add_argument("--null-order", dest="null_order", type=int, choices=(1, 2), default=None, metavar="{1,2}",
+                   help="with --shuffle-null: 1, mononucleotide shuffles (the default), or 2, shuffles that keep every "
+                        "sequence's doublet counts, first and last base -- the null for genomic peaks, whose CpG depletion "
+                        "and poly-A/T runs a mononucleotide shuffle destroys; both files then end in a null_order column")
     p.add_argument("--hit-pairs", action="store_true", dest="hit_pairs",
                    help="also write grafimo_hit_pairs.tsv (printed with -f): the pairs of report rows -- of one motif or of "
                         "two -- of a region that lie within --pair-gap of each other and share carrier haplotypes, with how "
@@ -342,6 +346,8 @@ def main(argv=None):
         sys.exit("ERROR: --null-seed goes with --shuffle-null")
     if a.null_seed is not None and not 0 <= a.null_seed < 2**64:
         sys.exit(f"ERROR: --null-seed {a.null_seed} outside [0, 2^64 - 1]")
+    if a.null_order is not None and a.shuffle_null is None:
+        sys.exit("ERROR: --null-order goes with --shuffle-null")
     if a.shuffle_null is not None and not 1 <= a.shuffle_null <= 2**20:
         sys.exit(f"ERROR: --shuffle-null {a.shuffle_null} outside [1, 2^20]")
     _graph_only(a, "shuffle_null")
@@ -563,7 +569,7 @@ def main(argv=None):
         graph, regions, first_index = source("shuffle_null")
         tables = compute_shuffle_null_many(motifs, graph, regions, a.debug, wf, haplotype_groups=groups(first_index),
                                            temperature=1.0 if a.affinity_temperature is None else a.affinity_temperature,
-                                           replicates=a.shuffle_null, seed=a.null_seed or 0)
+                                           replicates=a.shuffle_null, seed=a.null_seed or 0, order=a.null_order or 1)
         emit(tables, write_shuffle_null, print_shuffle_null, lambda t: f"{len(t)} shuffle null rows")
         if a.text_only:
             print_motif_enrichment(tables)

@@ -44,6 +44,7 @@ GFM_MUTSCAN_TILE = 64          # (the library's own decomposition: exported for 
 GFM_INDELSCAN_TILE = 64        # (as GFM_MUTSCAN_TILE)
 GFM_NULL_LDS_BASES = 960       # (the shuffle null's longest sequence shuffled in the LDS: exported for tests that aim at its edge)
 GFM_NULL_MAX_REPLICATES = 1 << 20
+GFM_NULL_MAX_WALK_CAP = 1024   # (order 2: the arborescence walks at most walk_cap x n steps a replicate)
 ABI_VERSION = 12
 RANGE = 1000
 
@@ -174,6 +175,9 @@ PROTOTYPES = {
     "gfm_sequence_shuffle_null": (c_int, [c_void_p, c_i32, c_void_p, c_u64, c_i32, c_void_p, c_void_p, c_void_p, c_void_p, c_i32,
                                           c_u64, c_void_p, ctypes.c_uint32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                           c_void_p, c_void_p, c_void_p, c_void_p]),
+    "gfm_sequence_shuffle_null_order": (c_int, [c_void_p, c_i32, c_void_p, c_u64, c_i32, c_void_p, c_void_p, c_void_p, c_void_p, c_i32,
+                                                c_u64, c_i32, c_i32, c_void_p, ctypes.c_uint32, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "gfm_hit_pairs": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_i32, c_i64, c_i64, c_i32, c_void_p, c_void_p, c_i64,
                               c_void_p, c_void_p, c_void_p, ctypes.c_uint32, P(c_i64), c_void_p]),
     "gfm_hit_linkage": (c_int, [c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_i64, c_i32, c_i32, c_i64,

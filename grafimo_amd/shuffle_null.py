@@ -27,11 +27,42 @@ scaled score in [0, L].
 Per (motif, sequence, replicate), when asked for: the dense rep_best int32 [S, K] and rep_sum uint64 [S, K].
 The result for one sequence depends on (seed, its key, its bytes, K, the motif, the weights, the flag) only.
 
+THE RULE OF ORDER 2 (order=2, --null-order 2; include/grafimo_hip.h states it for the library; tests/doublet_null_bruteforce.py
+on the host): the replicates keep x's doublets.  A mononucleotide shuffle destroys what real genomic sequence is made of -- CpG
+depletion, poly-A/T runs, simple repeats -- and so inflates the significance of every motif whose consensus holds a depleted or
+an enriched doublet.  mix, G, the key k, the seed and the replicates r are the order-1 rule's.
+  draw(t, m) = ((mix(s0 + t G) >> 32) m) >> 32, with m < 2^31.
+  Alphabet.  c[i] = base_code(x[i]): 0 .. 3 for A/C/G/T with case folded, 4 for anything else.  A replicate is a sequence of
+  codes.  Scores are taken on codes, as now.
+  Stream.  s0 = mix(mix(seed + k G) + r + 2^63).  The 2^63 separates the order-2 stream from the order-1 stream of the same
+  (seed, key, replicate).
+  Buckets.  cnt[a] = #{i < n - 1 : c[i] = a}; b[a] is the exclusive prefix sum over a = 0 .. 4.  E has length n - 1 and is the
+  stable counting sort of the successors: for i = 0 .. n - 2 in order, c[i + 1] is appended to bucket c[i].  E is the same for
+  all replicates of a sequence; the last entry of a bucket is x's own last exit from that symbol.
+  Arborescence.  Wilson's algorithm, rooted at root = c[n - 1].  in_tree = {root}, a step counter t = 0, cap = walk_cap n.
+  For u = 0 .. 4 in order, if cnt[u] > 0 and u is not in the tree: cur = u; while cur is not in the tree: if t == cap the
+  replicate is capped and the stage stops; else e = b[cur] + draw(n + t, cnt[cur]), t += 1, last[cur] = e, cur = E[e].  Then
+  retrace from u along E[last[.]], adding vertices to the tree.
+  A capped replicate takes last[a] = b[a + 1] - 1 for every a: x's own last exits, which always form an arborescence.
+  Per-bucket shuffle.  For a = 0 .. 4 with cnt[a] > 0: m = cnt[a]; if a != root, swap E[last[a]] with E[b[a + 1] - 1] and
+  m -= 1; for i = m - 1 down to 1: p = b[a] + i, j = draw(p, i + 1), swap E[p] and E[b[a] + j].  The Fisher-Yates counters
+  p <= n - 2 and the walk's counters >= n never meet.
+  Euler walk.  y[0] = c[0], ptr[a] = b[a]; for i = 1 .. n - 1: y[i] = E[ptr[y[i - 1]]], then ptr[y[i - 1]] += 1.  For n <= 1,
+  y = c.
+  Everything else is as order 1: the windows, the strands, min_val for a window with code 4, best, sum, obs_*, ge_* with ties
+  counting, rep_hits, rep_best, rep_sum, and n < W.
+Every replicate has x's length, first and last code and all 25 doublet counts of x; uncapped replicates are uniform over such
+sequences (Altschul and Erickson, with Wilson's arborescence) up to the multiply-shift bias.  The arborescence's walk is a
+random loop, so it is bounded by construction: walk_cap (default 64, in [0, 1024]; not a command-line option) is far from
+typical use -- a random 300-base sequence walks about 6 steps, (AC)^150 G about 300 --, and 0 caps every replicate.
+
 THE KEYS.  content_keys gives every sequence the key mix(sum over its offsets o of mix(upper(x[o]) + 256 o), plus n): equal
 sequences get equal nulls whatever call they are in, and whatever their neighbours.
 
 The hot path is HIP (grafimo_amd/csrc/gfm_graph_shuffle_null.hpp, gfm_sequence_shuffle_null): a wavefront takes 64 replicates of
-one sequence, a lane per replicate, shuffles them once for up to 16 motifs and slides every motif's window over each.
+one sequence, a lane per replicate, shuffles them once for up to 16 motifs and slides every motif's window over each.  Order 2
+(gfm_sequence_shuffle_null_order) replaces the fill and the shuffle: the wave sorts the successors into the image, each lane
+draws its arborescence, shuffles its buckets and walks; the scoring is the same code.
 Everything from the kernel's arrays to the frames is numpy; there is no Python step per sequence, replicate or base.
 """
 import contextlib
@@ -52,6 +83,8 @@ TABLE_FILE = "grafimo_shuffle_null"
 ENRICHMENT_FILE = "grafimo_motif_enrichment"
 DEFAULT_REPLICATES = 1000
 MAX_REPLICATES = nv.GFM_NULL_MAX_REPLICATES
+DEFAULT_WALK_CAP = 64
+MAX_WALK_CAP = nv.GFM_NULL_MAX_WALK_CAP
 G = np.uint64(0x9E3779B97F4A7C15)
 ENRICHMENT_COLUMNS = ["motif_id", "motif_alt_id", "width", "regions", "observed_hits", "null_mean_hits", "null_max_hits",
                       "enrichment_pvalue", "replicates"]
@@ -129,38 +162,51 @@ def _stage(tables, seq_offsets: np.ndarray, bases: np.ndarray, keys, seq_weights
             torch.zeros(1, dtype=torch.int32, device=dev))
 
 
-def _enqueue(dms, staged, K: int, seed: int, cuts, forward_only: bool):
-    """gfm_sequence_shuffle_null over staged inputs (_stage): every result tensor is overwritten -> the tensors by name"""
+def _checked_order(order, walk_cap=DEFAULT_WALK_CAP):
+    if order not in (1, 2):
+        raise ValueError(f"order {order}: the shuffle null is of order 1 (mononucleotide) or 2 (doublet-preserving)")
+    if not 0 <= int(walk_cap) <= MAX_WALK_CAP:
+        raise ValueError(f"walk_cap {walk_cap}: outside [0, {MAX_WALK_CAP}]")
+    return int(order), int(walk_cap)
+
+
+def _enqueue(dms, staged, K: int, seed: int, cuts, forward_only: bool, order: int = 1, walk_cap: int = DEFAULT_WALK_CAP):
+    """gfm_sequence_shuffle_null (order 1) or gfm_sequence_shuffle_null_order (order 2) over staged inputs (_stage): every
+    result tensor is overwritten -> the tensors by name"""
     seq_offsets, d_bases, d_keys, d_wts, d_tabs, max_weight, res, status = staged
     M = len(dms)
     vp = ctypes.c_void_p
     per_motif = lambda name: (vp * M)(*[res[name][m].data_ptr() if name in res else None for m in range(M)])     # noqa: E731
     h_cuts = np.ascontiguousarray(cuts, dtype=np.int32)
-    nv.check(nv.lib().gfm_sequence_shuffle_null(
+    entry, more = (nv.lib().gfm_sequence_shuffle_null, ()) if order == 1 else (nv.lib().gfm_sequence_shuffle_null_order,
+                                                                               (int(order), int(walk_cap)))
+    nv.check(entry(
         (vp * M)(*[x.handle for x in dms]), M, (vp * M)(*[t.data_ptr() for t in d_tabs]), max_weight, len(seq_offsets) - 1,
-        seq_offsets.ctypes.data, d_bases.data_ptr(), d_keys.data_ptr(), d_wts.data_ptr(), int(K), int(seed) & (2**64 - 1),
+        seq_offsets.ctypes.data, d_bases.data_ptr(), d_keys.data_ptr(), d_wts.data_ptr(), int(K), int(seed) & (2**64 - 1), *more,
         h_cuts.ctypes.data, nv.GFM_GRAPH_FORWARD_ONLY if forward_only else 0, *[per_motif(name) for name, _ in _RESULTS],
         status.data_ptr(), _stream_ptr(None)))
     return res
 
 
-def _launch(dms, tables, seq_offsets, bases, keys, seq_weights, K, seed, cuts, forward_only, keep) -> Dict[str, np.ndarray]:
-    """gfm_sequence_shuffle_null for leased motifs of one width over the sequences -> the arrays by name, each with the motif first"""
+def _launch(dms, tables, seq_offsets, bases, keys, seq_weights, K, seed, cuts, forward_only, keep, order=1,
+            walk_cap=DEFAULT_WALK_CAP) -> Dict[str, np.ndarray]:
+    """the kernel for leased motifs of one width over the sequences -> the arrays by name, each with the motif first"""
     M, S = len(dms), len(seq_offsets) - 1
     if S == 0:
         return {name: np.zeros(_shape(name, M, S, K), dtype=t) for name, t in _RESULTS[:7 if keep else 5]}
-    res = _enqueue(dms, _stage(tables, seq_offsets, bases, keys, seq_weights, K, keep), K, seed, cuts, forward_only)
+    res = _enqueue(dms, _stage(tables, seq_offsets, bases, keys, seq_weights, K, keep), K, seed, cuts, forward_only, order, walk_cap)
     return {name: res[name].cpu().numpy().view(t) for name, t in _RESULTS if name in res}
 
 
 def _null_chunked(motifs: Sequence, seq_offsets, bases, replicates, seed, seq_keys, seq_weights, cuts, threshold, weights,
-                  temperature, forward_only, keep, max_bytes):
+                  temperature, forward_only, keep, max_bytes, order=1, walk_cap=DEFAULT_WALK_CAP):
     """-> (per motif its dict of arrays (with "cut"), per motif its log2 offset, per motif (scale, offset, ptable)): the motifs
     leased (mutation_scan._leased_chunks) and the sequences taken in chunks whose device result tensors stay under max_bytes;
     rep_hits of sequence chunks are added here.  `cuts` None: pvalue_cut at `threshold`, or L without one."""
     S, K = len(seq_offsets) - 1, int(replicates)
     if not 1 <= K <= MAX_REPLICATES:
         raise ValueError(f"replicates {replicates}: outside [1, {MAX_REPLICATES}]")
+    order, walk_cap = _checked_order(order, walk_cap)
     keys = content_keys(seq_offsets, bases) if seq_keys is None else np.ascontiguousarray(seq_keys, dtype=np.uint64)
     wts = np.ones(S, dtype=np.uint32) if seq_weights is None else np.ascontiguousarray(seq_weights, dtype=np.uint32)
     if keys.shape != (S,) or wts.shape != (S,):
@@ -184,7 +230,7 @@ def _null_chunked(motifs: Sequence, seq_offsets, bases, replicates, seed, seq_ke
                 v1 = min(v0 + seq_step, S)
                 a, b = int(seq_offsets[v0]), int(seq_offsets[v1])
                 parts.append(_launch(dms, tables, np.ascontiguousarray(seq_offsets[v0:v1 + 1] - a), bases[a:b], keys[v0:v1],
-                                     wts[v0:v1], K, seed, cut, forward_only, keep))
+                                     wts[v0:v1], K, seed, cut, forward_only, keep, order, walk_cap))
             for m in range(len(dms)):
                 got = {name: np.concatenate([p[name][m] for p in parts], axis=0) for name in parts[0] if name != "rep_hits"}
                 got["rep_hits"] = np.sum([p["rep_hits"][m] for p in parts], axis=0, dtype=np.uint64)
@@ -197,7 +243,8 @@ def _null_chunked(motifs: Sequence, seq_offsets, bases, replicates, seed, seq_ke
 
 def null_sequences(motifs: Sequence, seq_offsets, bases, replicates: int, seed: int = 0, seq_keys=None, seq_weights=None, cuts=None,
                    weights: Optional[Sequence[np.ndarray]] = None, temperature: float = 1.0, forward_only: bool = False,
-                   keep_replicates: bool = False, max_bytes: int = DEFAULT_MAX_BYTES) -> List[Dict[str, np.ndarray]]:
+                   keep_replicates: bool = False, max_bytes: int = DEFAULT_MAX_BYTES, order: int = 1,
+                   walk_cap: int = DEFAULT_WALK_CAP) -> List[Dict[str, np.ndarray]]:
     """The kernel on plain arrays: sequences (`seq_offsets` int64 [S + 1] from 0, `bases` uint8) for motifs of ONE width -> per
     motif a dict: obs_best int32 [S], obs_sum uint64 [S], ge_best and ge_sum uint32 [S], rep_hits uint64 [K], cut (the scaled
     score rep_hits counted at), and with `keep_replicates` the dense rep_best int32 [S, K] and rep_sum uint64 [S, K].
@@ -205,11 +252,12 @@ def null_sequences(motifs: Sequence, seq_offsets, bases, replicates: int, seed: 
     default L (no replicate reaches it).  `weights`: a uint64 table per motif, default haplotype_affinity.default_weights at
     `temperature`.  Motifs and sequences are taken in chunks whose device result tensors stay under `max_bytes` (rep_hits of
     sequence chunks are added on the host; the result does not depend on the chunks); one sequence of one motif above it is a
-    ValueError that names it.  The library refuses motifs of two widths, replicates outside [1, 2^20], a cut outside [0, L]
-    and weights that can overflow a sum."""
+    ValueError that names it.  `order` 1: THE RULE; 2: THE RULE OF ORDER 2, doublet-preserving replicates, whose arborescence
+    walks at most `walk_cap` x n steps (in [0, 1024]; 0 caps every replicate).  The library refuses motifs of two widths,
+    replicates outside [1, 2^20], a cut outside [0, L] and weights that can overflow a sum."""
     seq_offsets, bases = _checked_sequences(seq_offsets, bases)
     return _null_chunked(motifs, seq_offsets, bases, replicates, seed, seq_keys, seq_weights, cuts, None, weights, temperature,
-                         forward_only, keep_replicates, max_bytes)[0]
+                         forward_only, keep_replicates, max_bytes, order, walk_cap)[0]
 
 
 # ---------------------------------------------------------------------------------------------------------------- the table
@@ -218,11 +266,13 @@ class ShuffleNull:
     Per sequence [S]: seq_region (the caller's region row), seq_version (the version's number in its region, -1: the region's
     reference sequence, which no haplotype spells), seq_count (haplotypes), seq_group_counts [S, G], seq_is_reference,
     seq_length -- as MutationScan's --, seq_weight (what the sequence counts for in rep_hits), and the kernel's obs_best int32,
-    obs_sum uint64, ge_best and ge_sum uint32.  Per replicate [K]: rep_hits uint64, counted at the scaled score `cut`."""
+    obs_sum uint64, ge_best and ge_sum uint32.  Per replicate [K]: rep_hits uint64, counted at the scaled score `cut`.
+    `order`: 1 or 2, the rule the replicates were made by."""
 
     def __init__(self, motif_id, motif_alt_id, width, scale, offset, ptable, log2_offset, threshold, region_names, group_names,
                  seq_region, seq_version, seq_count, seq_group_counts, seq_is_reference, seq_length, seq_weight, replicates, seed,
-                 obs_best, obs_sum, ge_best, ge_sum, rep_hits, cut):
+                 obs_best, obs_sum, ge_best, ge_sum, rep_hits, cut, order=1):
+        self.order = _checked_order(order)[0]
         self.motif_id, self.motif_alt_id = motif_id, motif_alt_id
         self.width, self.scale, self.offset = int(width), int(scale), float(offset)
         self.ptable, self.log2_offset, self.threshold = np.asarray(ptable, dtype=np.float64), float(log2_offset), float(threshold)
@@ -248,8 +298,9 @@ class ShuffleNull:
         """a row per (region, version): motif_id, motif_alt_id, sequence_name, version (-1: the reference sequence, no haplotype
         spells it), haplotypes, one haplotypes_<GROUP> per group, is_reference, length, best_score, best_pvalue (the tail
         table's per-window value at the best score), best_null_pvalue = (1 + ge_best) / (K + 1), log2_affinity,
-        affinity_null_pvalue = (1 + ge_sum) / (K + 1), replicates -- NaN where the sequence is shorter than the motif.  The
-        sequences by region, then version, the reference sequence last."""
+        affinity_null_pvalue = (1 + ge_sum) / (K + 1), replicates -- NaN where the sequence is shorter than the motif --, and
+        under order 2 one more last column, null_order = 2.  The sequences by region, then version, the reference sequence
+        last."""
         S = len(self)
         best = self.obs_best.astype(np.int64)
         some = self.seq_length >= self.width
@@ -267,6 +318,8 @@ class ShuffleNull:
         data["log2_affinity"] = np.where(filled, np.log2(np.where(filled, self.obs_sum, 1).astype(np.float64)) + self.log2_offset, np.nan)
         data["affinity_null_pvalue"] = np.where(some, null_pvalues(self.ge_sum, self.replicates), np.nan)
         data["replicates"] = np.full(S, self.replicates, dtype=np.int64)
+        if self.order != 1:
+            data["null_order"] = np.full(S, self.order, dtype=np.int64)
         return pd.DataFrame(data)
 
 
@@ -274,7 +327,7 @@ def enrichment_frame(tables: Sequence[ShuffleNull]) -> pd.DataFrame:
     """One row per motif for the whole call, in the motifs' order: motif_id, motif_alt_id, width, regions (the sequences that
     count), observed_hits = the seq_weight of the sequences whose own best score reaches the cut, null_mean_hits and
     null_max_hits over the replicates' rep_hits, enrichment_pvalue = (1 + #{r : rep_hits[r] >= observed_hits}) / (K + 1),
-    replicates.
+    replicates -- and one more last column, null_order = 2, when the tables are of order 2.
     compute_shuffle_null_many gives seq_weight 1 to each region's version 0, its most frequent spelled sequence, and 0 to every
     other: a region is ONE draw.  The versions of a region are nearly the same sequence, and independent shuffles of each would
     be counted as independent regions -- the pooled count's variance would be understated and the p-value too small.
@@ -286,21 +339,24 @@ def enrichment_frame(tables: Sequence[ShuffleNull]) -> pd.DataFrame:
         hits = t.rep_hits.astype(np.float64)
         rows.append((t.motif_id, t.motif_alt_id, t.width, int((w > 0).sum()), observed, float(hits.mean()), int(t.rep_hits.max()),
                      float(null_pvalues(int((t.rep_hits >= np.uint64(observed)).sum()), t.replicates)), t.replicates))
-    return pd.DataFrame(rows, columns=ENRICHMENT_COLUMNS).astype({"width": np.int64, "regions": np.int64, "observed_hits": np.int64,
-                                                                  "null_mean_hits": np.float64, "null_max_hits": np.int64,
-                                                                  "enrichment_pvalue": np.float64, "replicates": np.int64})
+    frame = pd.DataFrame(rows, columns=ENRICHMENT_COLUMNS).astype({"width": np.int64, "regions": np.int64, "observed_hits": np.int64,
+                                                                   "null_mean_hits": np.float64, "null_max_hits": np.int64,
+                                                                   "enrichment_pvalue": np.float64, "replicates": np.int64})
+    if any(t.order != 1 for t in tables):
+        frame["null_order"] = np.array([t.order for t in tables], dtype=np.int64)
+    return frame
 
 
 def compute_shuffle_null_many(motifs: Sequence, graph, regions, debug: bool, args_obj, chrom_names=None,
                               haplotype_groups: Optional[Mapping] = None, weights: Optional[Sequence[np.ndarray]] = None,
                               temperature: float = 1.0, threshold: Optional[float] = None, replicates: int = DEFAULT_REPLICATES,
-                              seed: int = 0, max_bytes: int = DEFAULT_MAX_BYTES) -> List[ShuffleNull]:
+                              seed: int = 0, max_bytes: int = DEFAULT_MAX_BYTES, order: int = 1) -> List[ShuffleNull]:
     """One ShuffleNull per motif, in the order of `motifs` (see the module's docstring).  The arguments and the sequences are
     compute_mutation_scan_many's: the versions of compute_haplotype_sequences(coordinates=True), the reference sequence of a
     region added with count 0 where no version is the reference's; one kernel call per motif width (in chunks under
     `max_bytes`).  The keys are content_keys; seq_weight is 1 for each region's version 0 and 0 elsewhere (enrichment_frame says
     why); the cut is pvalue_cut at the threshold.  args_obj: noreverse and threshold (`threshold` overrides it).
-    `temperature` / `weights` as compute_haplotype_affinity_many's."""
+    `temperature` / `weights` as compute_haplotype_affinity_many's.  `order`: 1, or 2 for doublet-preserving replicates."""
     from .haplotype_classes import compute_haplotype_classes
     from .haplotype_sequences import compute_haplotype_sequences
     require_single_gpu("the shuffle null", "is", "a gather of the sharded class matrices")
@@ -308,6 +364,7 @@ def compute_shuffle_null_many(motifs: Sequence, graph, regions, debug: bool, arg
         raise ValueError(f"{len(weights)} weight tables for {len(motifs)} motifs")
     if not 1 <= int(replicates) <= MAX_REPLICATES:
         raise ValueError(f"replicates {replicates}: outside [1, {MAX_REPLICATES}]")
+    order = _checked_order(order)[0]
     prep = prepare_graphs(graph, regions, chrom_names)
     _haplotype_set(prep, None, "the shuffle null")
     rows, region_names = _matrix_rows(prep)
@@ -323,22 +380,24 @@ def compute_shuffle_null_many(motifs: Sequence, graph, regions, debug: bool, arg
     for W, idxs in group_by_width(motifs).items():
         got, offsets, numbers = _null_chunked([motifs[i] for i in idxs], seq_offsets, bases, replicates, seed, keys, seq_weight, None,
                                               threshold, None if weights is None else [weights[i] for i in idxs], temperature,
-                                              forward_only, False, max_bytes)
+                                              forward_only, False, max_bytes, order)
         for m, i in enumerate(idxs):
             scale, offset, ptable = numbers[m]
             g = got[m]
             out[i] = ShuffleNull(motifs[i].motif_id, motifs[i].motif_name, W, scale, offset, ptable, offsets[m], threshold,
                                  region_names, hs.group_names, *seqs[:5], np.diff(seq_offsets), seq_weight, replicates, seed,
-                                 g["obs_best"], g["obs_sum"], g["ge_best"], g["ge_sum"], g["rep_hits"], g["cut"])
+                                 g["obs_best"], g["obs_sum"], g["ge_best"], g["ge_sum"], g["rep_hits"], g["cut"], order)
     return out
 
 
 def compute_shuffle_null(motif, graph, regions, debug: bool, args_obj, chrom_names=None, haplotype_groups: Optional[Mapping] = None,
                          weights: Optional[np.ndarray] = None, temperature: float = 1.0, threshold: Optional[float] = None,
-                         replicates: int = DEFAULT_REPLICATES, seed: int = 0, max_bytes: int = DEFAULT_MAX_BYTES) -> ShuffleNull:
+                         replicates: int = DEFAULT_REPLICATES, seed: int = 0, max_bytes: int = DEFAULT_MAX_BYTES,
+                         order: int = 1) -> ShuffleNull:
     """The shuffle null of `motif` (compute_shuffle_null_many for one motif)"""
     return compute_shuffle_null_many([motif], graph, regions, debug, args_obj, chrom_names, haplotype_groups,
-                                     None if weights is None else [weights], temperature, threshold, replicates, seed, max_bytes)[0]
+                                     None if weights is None else [weights], temperature, threshold, replicates, seed, max_bytes,
+                                     order)[0]
 
 
 # ---------------------------------------------------------------------------------------------------------------- the writers

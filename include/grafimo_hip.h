@@ -972,6 +972,46 @@ int gfm_sequence_shuffle_null(const gfm_motif_t *motifs, int32_t n_motifs, const
                               uint32_t *const *d_ge_sum, uint64_t *const *d_rep_hits, int32_t *const *d_rep_best,
                               uint64_t *const *d_rep_sum, int32_t *d_status, void *stream);
 
+/* ------------------------------------------------------------------ shuffle null of order 2: doublet-preserving replicates
+ * gfm_sequence_shuffle_null with two more arguments: order 1 is THE RULE above, bit for bit (walk_cap is then not used);
+ * order 2 makes the replicates by THE RULE OF ORDER 2.  mix, G, the key k, the seed and the replicates r are the order-1
+ * rule's; all arithmetic on 64-bit words is modulo 2^64.
+ *   draw(t, m) = ((mix(s0 + t G) >> 32) m) >> 32, with m < 2^31.
+ *   Alphabet.  c[i] = base_code(x[i]): 0 .. 3 for A/C/G/T with case folded, 4 for anything else.  A replicate is a sequence of
+ *   codes.  Scores are taken on codes, as now.
+ *   Stream.  s0 = mix(mix(seed + k G) + r + 2^63).  The 2^63 separates the order-2 stream from the order-1 stream of the same
+ *   (seed, key, replicate).
+ *   Buckets.  cnt[a] = #{i < n - 1 : c[i] = a}; b[a] is the exclusive prefix sum over a = 0 .. 4.  E has length n - 1 and is
+ *   the stable counting sort of the successors: for i = 0 .. n - 2 in order, c[i + 1] is appended to bucket c[i].  E is the
+ *   same for all replicates of a sequence; the last entry of a bucket is x's own last exit from that symbol.
+ *   Arborescence.  Wilson's algorithm, rooted at root = c[n - 1].  in_tree = {root}, a step counter t = 0, cap = walk_cap n.
+ *   For u = 0 .. 4 in order, if cnt[u] > 0 and u is not in the tree: cur = u; while cur is not in the tree: if t == cap the
+ *   replicate is capped and the stage stops; else e = b[cur] + draw(n + t, cnt[cur]), t += 1, last[cur] = e, cur = E[e].  Then
+ *   retrace from u along E[last[.]], adding vertices to the tree.
+ *   A capped replicate takes last[a] = b[a + 1] - 1 for every a: x's own last exits, which always form an arborescence.
+ *   Per-bucket shuffle.  For a = 0 .. 4 with cnt[a] > 0: m = cnt[a]; if a != root, swap E[last[a]] with E[b[a + 1] - 1] and
+ *   m -= 1; for i = m - 1 down to 1: p = b[a] + i, j = draw(p, i + 1), swap E[p] and E[b[a] + j].  The Fisher-Yates counters
+ *   p <= n - 2 and the walk's counters >= n never meet.
+ *   Euler walk.  y[0] = c[0], ptr[a] = b[a]; for i = 1 .. n - 1: y[i] = E[ptr[y[i - 1]]], then ptr[y[i - 1]] += 1.  For n <= 1,
+ *   y = c.
+ *   Everything else is as order 1: the windows, the strands, min_val for a window with code 4, best, sum, obs_*, ge_* with ties
+ *   counting, rep_hits, rep_best, rep_sum, and n < W.
+ * Every replicate has x's length, first and last code and all 25 doublet counts of x; uncapped replicates are uniform over such
+ * sequences (Altschul and Erickson, with Wilson's arborescence) up to the multiply-shift bias.  The cap bounds the walk by
+ * construction: t and cap are 64-bit, walk_cap lies in [0, GFM_NULL_MAX_WALK_CAP], 64 is far from typical use (a random
+ * 300-base sequence walks about 6 steps, (AC)^150 G about 300), 0 caps every replicate.
+ * The image, GFM_NULL_LDS_BASES and the memory path are order 1's (the E codes share the image's bytes).  GFM_ERR_INVALID
+ * besides gfm_sequence_shuffle_null's: an order that is neither 1 nor 2, a walk_cap outside the range; the message names the
+ * value. */
+#define GFM_NULL_MAX_WALK_CAP 1024
+int gfm_sequence_shuffle_null_order(const gfm_motif_t *motifs, int32_t n_motifs, const uint64_t *const *d_weights,
+                                    uint64_t max_weight, int32_t n_seqs, const int64_t *seq_offsets, const uint8_t *d_bases,
+                                    const uint64_t *d_seq_keys, const uint32_t *d_seq_weight, int32_t n_replicates, uint64_t seed,
+                                    int32_t order, int32_t walk_cap, const int32_t *cuts, uint32_t flags,
+                                    int32_t *const *d_obs_best, uint64_t *const *d_obs_sum, uint32_t *const *d_ge_best,
+                                    uint32_t *const *d_ge_sum, uint64_t *const *d_rep_hits, int32_t *const *d_rep_best,
+                                    uint64_t *const *d_rep_sum, int32_t *d_status, void *stream);
+
 /* ------------------------------------------------------------------ hit pairs: rows close to each other that share carriers
  * Graph-independent (csrc/hit_pairs.hip).  n rows (n < 2^31 - 1) in device memory, in ascending (d_group, d_lo) order:
  * d_group int32, d_lo <= d_hi int64 (|x| < 2^61), d_masks uint64 [n][hw] (hw >= 1 words of a bitset whose unused tail

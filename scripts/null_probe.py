@@ -5,10 +5,12 @@ clears the counters, uploads its sequence table, launches per length class, copi
 figure is the kernels plus some tens of microseconds), and the ratio of the 16-motif median to the 1-motif median -- 16 if the
 shuffle cost nothing, 1 if it cost everything.  Then the same for --long-length bases (the scratch path) at a tenth of the
 sequences, and the LDS-instruction floor of the shape (DESIGN 3.22 derives it).  --no-reverse scores the + strand only: the same
-LDS work with one weight gather a window instead of two, which shows what the gathers cost.
+LDS work with one weight gather a window instead of two, which shows what the gathers cost.  --order 2 makes the replicates
+doublet-preserving: what is made once per launch is then the counting sort, the arborescence, the bucket shuffles
+and the walk; the floor printed is order 1's.
 
     python scripts/null_probe.py [--seqs 2000] [--length 300] [--replicates 1024] [--width 19] [--reps 5] [--warmup 2]
-                                 [--no-reverse] [--out FILE]
+                                 [--order 1] [--no-reverse] [--out FILE]
 """
 import argparse
 import os
@@ -43,6 +45,7 @@ def main():
     ap.add_argument("--width", type=int, default=19)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--order", type=int, choices=(1, 2), default=1, help="2: doublet-preserving replicates")
     ap.add_argument("--no-reverse", action="store_true", help="+ strand only: one weight gather a window instead of two")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
@@ -54,7 +57,8 @@ def main():
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     from extract_fuzz_core import SynMotif
 
-    lines = [f"{torch.cuda.get_device_name(0)}: W = {a.width}, K = {a.replicates}, {'+ strand only' if a.no_reverse else 'both strands'}"]
+    lines = [f"{torch.cuda.get_device_name(0)}: W = {a.width}, K = {a.replicates}, {'+ strand only' if a.no_reverse else 'both strands'}"
+             + (f", order {a.order}" if a.order != 1 else "")]
     rng = np.random.default_rng(1)
     W, K = a.width, a.replicates
     motifs = [SynMotif(W, seed=900 + k) for k in range(16)]
@@ -68,12 +72,13 @@ def main():
             med = {}
             for M in (1, 16):
                 staged = sn._stage(tables[:M], off, bases, keys, np.ones(n_seqs, dtype=np.uint32), K, False)
-                run = lambda: sn._enqueue(dms[:M], staged, K, 0, [9000] * M, a.no_reverse)     # noqa: E731
+                run = lambda: sn._enqueue(dms[:M], staged, K, 0, [9000] * M, a.no_reverse, a.order)     # noqa: E731
                 med[M], lo, hi = _timed(run, a.warmup, a.reps)
                 windows = n_seqs * K * (length - W + 1)
                 lines.append(f"{n_seqs} sequences of {length} bases, {M:2d} motifs: median {med[M]:9.3f} ms (min {lo:.3f}, max {hi:.3f}), "
                              f"{M * windows / med[M] / 1e6:8.1f} G windows/s")
-            lines.append(f"{n_seqs} sequences of {length} bases: 16 motifs / 1 motif = {med[16] / med[1]:.2f}")
+            lines.append(f"{n_seqs} sequences of {length} bases: 16 motifs / 1 motif = {med[16] / med[1]:.2f}; a further motif "
+                         f"{(med[16] - med[1]) / 15:.3f} ms, made once {med[1] - (med[16] - med[1]) / 15:.3f} ms")
             # the floor: a window column costs the lane a byte read of its code and a word read of the table row, a swap two
             # byte reads and two byte stores: wave-instructions on the LDS, at best 2 array cycles each, a CU's LDS one at a time
             waves = n_seqs * ((K + 63) // 64)
