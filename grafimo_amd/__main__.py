@@ -112,7 +112,7 @@ def get_parser():
                         "haplotype's total binding affinity -- the sum of 2^(log-odds / T) over every k-mer of its own "
                         "sequence --, beside the reference's (graph routes only)")
     p.add_argument("--affinity-temperature", dest="affinity_temperature", type=float, default=None, metavar="T",
-                   help="with --haplotype-affinity, --variant-affinity, --haplotype-classes, --query-variants, --mutation-scan, --indel-scan or --shuffle-null: the temperature T > 0 the log-odds scores are "
+                   help="with --haplotype-affinity, --variant-affinity, --haplotype-classes, --query-variants, --mutation-scan, --indel-scan, --deletion-scan or --shuffle-null: the temperature T > 0 the log-odds scores are "
                         "divided by; default 1")
     p.add_argument("--variant-affinity", action="store_true", dest="variant_affinity",
                    help="also write grafimo_variant_affinity[_MOTIF].tsv (printed with -f): per variant, the log2 of the mean "
@@ -124,7 +124,7 @@ def get_parser():
                    help="also write grafimo_hit_alleles[_MOTIF].tsv (printed with -f): the report's rows, each with the variant "
                         "alleles that make its k-mer and, with --haplotype-groups, its carriers per group (graph routes only)")
     p.add_argument("--haplotype-groups", dest="haplotype_groups", metavar="FILE",
-                   help="with --hit-alleles, --hit-pairs, --haplotype-classes, --haplotype-sequences, --query-variants, --mutation-scan, --indel-scan or --shuffle-null: SAMPLE GROUP lines (the 1000 Genomes panel file reads as is), one "
+                   help="with --hit-alleles, --hit-pairs, --haplotype-classes, --haplotype-sequences, --query-variants, --mutation-scan, --indel-scan, --deletion-scan or --shuffle-null: SAMPLE GROUP lines (the 1000 Genomes panel file reads as is), one "
                         "haplotypes_GROUP column per group")
     p.add_argument("--haplotype-classes", action="store_true", dest="haplotype_classes",
                    help="also write grafimo_haplotype_classes[_MOTIF].tsv (printed with -f) and "
@@ -170,6 +170,18 @@ def get_parser():
                    help="with --indel-scan: also keep the rows with |delta_log2_affinity| >= X")
     p.add_argument("--indel-all", action="store_true", dest="indel_all",
                    help="with --indel-scan: keep every row, up to five per base")
+    p.add_argument("--deletion-scan", dest="deletion_scan", nargs="+", type=int, default=None, metavar="L",
+                   help="also write grafimo_deletion_scan[_MOTIF].tsv and grafimo_deletion_scan_summary[_MOTIF].tsv (printed "
+                        "with -f): the indel scan's companion for block deletions -- the deletion of every block of L bases, "
+                        "for each given L in 1 .. 64 (duplicates are merged, the list is sorted), at every offset of every "
+                        "sequence the haplotypes spell in a region (inserted bases too) and of the reference sequence, with "
+                        "the best hit and the total affinity before and after, the effect, and the haplotypes that spell the "
+                        "sequence, in all and per --haplotype-groups group; rows are kept on gain or loss; in a repeat a "
+                        "deletion is reported once, at its leftmost offset (graph routes only)")
+    p.add_argument("--deletion-delta", dest="deletion_delta", type=float, default=None, metavar="X",
+                   help="with --deletion-scan: also keep the rows with |delta_log2_affinity| >= X")
+    p.add_argument("--deletion-all", action="store_true", dest="deletion_all",
+                   help="with --deletion-scan: keep every row, up to one per base and length")
     p.add_argument("--shuffle-null", dest="shuffle_null", nargs="?", type=int, const=1000, default=None, metavar="K",
                    help="also write grafimo_shuffle_null[_MOTIF].tsv and grafimo_motif_enrichment.tsv (printed with -f): every "
                         "sequence the haplotypes spell in a region, and the reference sequence, against K (default 1000) "
@@ -262,7 +274,8 @@ _GRAPH_TABLES = {"variant_effects": ("--variant-effects", "alleles"), "haplotype
                  "haplotype_classes": ("--haplotype-classes", "haplotypes"),
                  "haplotype_sequences": ("--haplotype-sequences", "haplotypes"),
                  "query_variants": ("--query-variants", "haplotypes"), "mutation_scan": ("--mutation-scan", "haplotypes"),
-                 "indel_scan": ("--indel-scan", "haplotypes"), "shuffle_null": ("--shuffle-null", "haplotypes")}
+                 "indel_scan": ("--indel-scan", "haplotypes"), "deletion_scan": ("--deletion-scan", "haplotypes"),
+                 "shuffle_null": ("--shuffle-null", "haplotypes")}
 
 
 def _graph_only(a, table):
@@ -301,7 +314,8 @@ def main(argv=None):
     _graph_only(a, "haplotype_hits")
     _graph_only(a, "haplotype_scores")
     if a.affinity_temperature is not None and not (a.haplotype_affinity or a.variant_affinity or a.haplotype_classes
-                                                    or a.query_variants or a.mutation_scan or a.indel_scan or a.shuffle_null):
+                                                    or a.query_variants or a.mutation_scan or a.indel_scan or a.deletion_scan
+                                                    or a.shuffle_null):
         sys.exit("ERROR: --affinity-temperature goes with --haplotype-affinity or --variant-affinity or --haplotype-classes")
     if a.affinity_temperature is not None and not a.affinity_temperature > 0:
         sys.exit(f"ERROR: --affinity-temperature {a.affinity_temperature} is not > 0")
@@ -312,7 +326,8 @@ def main(argv=None):
         sys.exit(f"ERROR: --variant-affinity-delta {a.variant_affinity_delta} is not >= 0")
     _graph_only(a, "variant_affinity")
     if a.haplotype_groups and not (a.hit_alleles or a.hit_pairs or a.haplotype_classes or a.haplotype_sequences
-                                   or a.query_variants or a.mutation_scan or a.indel_scan or a.shuffle_null):
+                                   or a.query_variants or a.mutation_scan or a.indel_scan or a.deletion_scan
+                                   or a.shuffle_null):
         sys.exit("ERROR: --haplotype-groups goes with --hit-alleles or --hit-pairs or --haplotype-classes or "
                  "--haplotype-sequences")
     if a.class_min_haplotypes is not None and not a.haplotype_classes:
@@ -342,6 +357,18 @@ def main(argv=None):
     if a.indel_delta is not None and not a.indel_delta >= 0:
         sys.exit(f"ERROR: --indel-delta {a.indel_delta} is not >= 0")
     _graph_only(a, "indel_scan")
+    if a.deletion_all and not a.deletion_scan:
+        sys.exit("ERROR: --deletion-all goes with --deletion-scan")
+    if a.deletion_delta is not None and not a.deletion_scan:
+        sys.exit("ERROR: --deletion-delta goes with --deletion-scan")
+    if a.deletion_delta is not None and not a.deletion_delta >= 0:
+        sys.exit(f"ERROR: --deletion-delta {a.deletion_delta} is not >= 0")
+    if a.deletion_scan:
+        bad = [L for L in a.deletion_scan if not 1 <= L <= 64]
+        if bad:
+            sys.exit(f"ERROR: --deletion-scan {bad[0]}: a length lies in 1 .. 64")
+        a.deletion_scan = sorted(set(a.deletion_scan))
+    _graph_only(a, "deletion_scan")
     if a.null_seed is not None and a.shuffle_null is None:
         sys.exit("ERROR: --null-seed goes with --shuffle-null")
     if a.null_seed is not None and not 0 <= a.null_seed < 2**64:
@@ -563,6 +590,18 @@ def main(argv=None):
             for motif, t in zip(motifs, tables):
                 print(f"{len(t.summary_frame())} indel scan summary rows written to "
                       f"{write_indel_scan_summary(t, motif, len(motifs), wf)}")
+    if a.deletion_scan:
+        from .deletion_scan import (compute_deletion_scan_many, print_deletion_scan, write_deletion_scan,
+                                    write_deletion_scan_summary)
+        graph, regions, first_index = source("deletion_scan")
+        tables = compute_deletion_scan_many(motifs, graph, regions, a.debug, wf, a.deletion_scan, haplotype_groups=groups(first_index),
+                                            temperature=1.0 if a.affinity_temperature is None else a.affinity_temperature,
+                                            delta=a.deletion_delta, all_rows=a.deletion_all)
+        emit(tables, write_deletion_scan, print_deletion_scan, lambda t: f"{len(t)} deletion scan rows")
+        if not a.text_only:
+            for motif, t in zip(motifs, tables):
+                print(f"{len(t.summary_frame())} deletion scan summary rows written to "
+                      f"{write_deletion_scan_summary(t, motif, len(motifs), wf)}")
     if a.shuffle_null is not None:                     # (a table per motif, and one row per motif for the whole call)
         from .shuffle_null import (compute_shuffle_null_many, print_motif_enrichment, print_shuffle_null, write_motif_enrichment,
                                    write_shuffle_null)

@@ -925,6 +925,42 @@ int gfm_sequence_indel_scan(const gfm_motif_t *motifs, int32_t n_motifs, const u
                             int32_t n_seqs, const int64_t *seq_offsets, const uint8_t *d_bases, uint32_t flags,
                             uint32_t *const *d_keys, uint64_t *const *d_sums, int32_t *d_status, void *stream);
 
+/* ------------------------------------------------------------------ deletion scan: every block deletion of 1 .. 64 bases of a spelled sequence
+ * Graph-independent.  THE RULE.  For a sequence x of n bases, a motif of width W, a strictly ascending list of lengths
+ * L0 < L1 < .. with every L in 1 .. GFM_DELSCAN_MAX_LENGTH, every length L of the list and every offset o in 0 .. n - 1:
+ *   If o + L > n there is no edit: both keys and both sums of the cell are 0.
+ *   Otherwise y = x[:o] + x[o+L:].  This is gfm_graph_query_edits' rule with lr = L, la = 0 at offset o.
+ *     REF side (column COVER): the starts s of x with max(0, o - W + 1) <= s <= min(o + L - 1, n - W).
+ *     ALT side (column DEL): the starts of y across the junction, max(0, o - W + 1) <= s <= min(o - 1, n - L - W).
+ *   Every window is scored once per strand, or + only under GFM_GRAPH_FORWARD_ONLY.
+ *   A window that holds a base that is not A/C/G/T scores min_val on both strands.  Case is folded, as base_code does.
+ *   A deleted N can repair its junction windows.  An N elsewhere cannot be repaired.
+ *   Per column, the best window by (score descending, s ascending, + before -), as the key
+ *   ((score + 1) << 8) | ((64 - (s - o)) << 1) | plus, s - o in -(W - 1) .. L - 1 for COVER and in -(W - 1) .. -1 for DEL: the
+ *   values a gfm_edit_record_t of the same edit holds.  Key 0 means the side has no window.
+ *   Per column, the exact uint64 sum of w[score] over the side's windows and strands.
+ *   At L = 1 the two columns equal gfm_sequence_indel_scan's COVER and DEL bit for bit.
+ * By construction a cell equals, field for field, what gfm_graph_query_edits returns for the deletion (coordinate of o,
+ * x[o .. o + L - 1], "") applied to x, wherever coordinates can name the block (GFM_QUERY_MAX_ALLELE is 64 as well, and the
+ * key's 7-bit field holds every s - o that occurs).
+ *
+ * The arguments are gfm_sequence_indel_scan's and n_lengths >= 1 with lengths, int32 [n_lengths] on the HOST.  Refused when
+ * max_weight * 2 * (W + Lmax - 1) passes 2^64 - 1, Lmax the longest length: a REF side has at most W + Lmax - 1 windows.
+ * d_keys[m] uint32 [n_lengths][seq_offsets[n_seqs]][2], 8-byte aligned, and d_sums[m] uint64 of the same shape, 16-byte
+ * aligned: per length and base of d_bases the columns COVER, DEL.  Every cell is written, nothing is zeroed by the caller.
+ * The work is cut into (sequence, GFM_DELSCAN_TILE offsets) tiles by the library; the result does not depend on the tile -- it
+ * is exported only so that tests can aim at its edges.  No sequence or no base returns GFM_OK and touches nothing.
+ * GFM_ERR_INVALID, all before anything is launched: a NULL pointer, lengths that do not strictly ascend or lie outside
+ * 1 .. GFM_DELSCAN_MAX_LENGTH, motifs of different widths or on another device than the current one, weights that can overflow
+ * a sum, offsets that descend, a sequence of 2^31 bases or more, a misaligned result, an unknown flag.  The call WAITS for the
+ * stream (it reads the verdict of the device's check of the tile table). */
+#define GFM_DELSCAN_TILE 64
+#define GFM_DELSCAN_MAX_LENGTH 64
+int gfm_sequence_deletion_scan(const gfm_motif_t *motifs, int32_t n_motifs, const uint64_t *const *d_weights, uint64_t max_weight,
+                               int32_t n_seqs, const int64_t *seq_offsets, const uint8_t *d_bases, int32_t n_lengths,
+                               const int32_t *lengths, uint32_t flags, uint32_t *const *d_keys, uint64_t *const *d_sums,
+                               int32_t *d_status, void *stream);
+
 /* ------------------------------------------------------------------ shuffle null: empirical p-values for best score and total affinity
  * Graph-independent.  THE RULE.  All arithmetic on 64-bit words is modulo 2^64.
  *   G = 0x9E3779B97F4A7C15.
