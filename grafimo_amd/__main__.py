@@ -112,7 +112,7 @@ def get_parser():
                         "haplotype's total binding affinity -- the sum of 2^(log-odds / T) over every k-mer of its own "
                         "sequence --, beside the reference's (graph routes only)")
     p.add_argument("--affinity-temperature", dest="affinity_temperature", type=float, default=None, metavar="T",
-                   help="with --haplotype-affinity, --variant-affinity, --haplotype-classes, --query-variants, --mutation-scan, --indel-scan, --deletion-scan or --shuffle-null: the temperature T > 0 the log-odds scores are "
+                   help="with --haplotype-affinity, --variant-affinity, --haplotype-classes, --query-variants, --mutation-scan, --indel-scan, --deletion-scan, --substitution-scan or --shuffle-null: the temperature T > 0 the log-odds scores are "
                         "divided by; default 1")
     p.add_argument("--variant-affinity", action="store_true", dest="variant_affinity",
                    help="also write grafimo_variant_affinity[_MOTIF].tsv (printed with -f): per variant, the log2 of the mean "
@@ -124,7 +124,7 @@ def get_parser():
                    help="also write grafimo_hit_alleles[_MOTIF].tsv (printed with -f): the report's rows, each with the variant "
                         "alleles that make its k-mer and, with --haplotype-groups, its carriers per group (graph routes only)")
     p.add_argument("--haplotype-groups", dest="haplotype_groups", metavar="FILE",
-                   help="with --hit-alleles, --hit-pairs, --haplotype-classes, --haplotype-sequences, --query-variants, --mutation-scan, --indel-scan, --deletion-scan or --shuffle-null: SAMPLE GROUP lines (the 1000 Genomes panel file reads as is), one "
+                   help="with --hit-alleles, --hit-pairs, --haplotype-classes, --haplotype-sequences, --query-variants, --mutation-scan, --indel-scan, --deletion-scan, --substitution-scan or --shuffle-null: SAMPLE GROUP lines (the 1000 Genomes panel file reads as is), one "
                         "haplotypes_GROUP column per group")
     p.add_argument("--haplotype-classes", action="store_true", dest="haplotype_classes",
                    help="also write grafimo_haplotype_classes[_MOTIF].tsv (printed with -f) and "
@@ -182,6 +182,21 @@ def get_parser():
                    help="with --deletion-scan: also keep the rows with |delta_log2_affinity| >= X")
     p.add_argument("--deletion-all", action="store_true", dest="deletion_all",
                    help="with --deletion-scan: keep every row, up to one per base and length")
+    p.add_argument("--substitution-scan", dest="substitution_scan", nargs="+", type=int, default=None, metavar="L",
+                   help="also write grafimo_substitution_scan[_MOTIF].tsv and grafimo_substitution_scan_summary[_MOTIF].tsv "
+                        "(printed with -f): the deletion scan's companion for blocks replaced in place -- every block of L "
+                        "bases, for each given L in 1 .. 64 (duplicates are merged, the list is sorted), replaced by its image "
+                        "under --substitution-map at every offset of every sequence the haplotypes spell in a region (inserted "
+                        "bases too) and of the reference sequence, with the best hit and the total affinity before and after, "
+                        "the effect, and the haplotypes that spell the sequence, in all and per --haplotype-groups group; rows "
+                        "are kept on gain or loss; a block the map does not change is no row (graph routes only)")
+    p.add_argument("--substitution-map", dest="substitution_map", default=None, metavar="MAP",
+                   help="with --substitution-scan: transversion (A>C C>A G>T T>G), complement, transition, or the images of "
+                        "A, C, G, T as four letters over ACGT, such as AAAA for a poly-A linker; default transversion")
+    p.add_argument("--substitution-delta", dest="substitution_delta", type=float, default=None, metavar="X",
+                   help="with --substitution-scan: also keep the rows with |delta_log2_affinity| >= X")
+    p.add_argument("--substitution-all", action="store_true", dest="substitution_all",
+                   help="with --substitution-scan: keep every row, up to one per base and length")
     p.add_argument("--shuffle-null", dest="shuffle_null", nargs="?", type=int, const=1000, default=None, metavar="K",
                    help="also write grafimo_shuffle_null[_MOTIF].tsv and grafimo_motif_enrichment.tsv (printed with -f): every "
                         "sequence the haplotypes spell in a region, and the reference sequence, against K (default 1000) "
@@ -275,6 +290,7 @@ _GRAPH_TABLES = {"variant_effects": ("--variant-effects", "alleles"), "haplotype
                  "haplotype_sequences": ("--haplotype-sequences", "haplotypes"),
                  "query_variants": ("--query-variants", "haplotypes"), "mutation_scan": ("--mutation-scan", "haplotypes"),
                  "indel_scan": ("--indel-scan", "haplotypes"), "deletion_scan": ("--deletion-scan", "haplotypes"),
+                 "substitution_scan": ("--substitution-scan", "haplotypes"),
                  "shuffle_null": ("--shuffle-null", "haplotypes")}
 
 
@@ -315,7 +331,7 @@ def main(argv=None):
     _graph_only(a, "haplotype_scores")
     if a.affinity_temperature is not None and not (a.haplotype_affinity or a.variant_affinity or a.haplotype_classes
                                                     or a.query_variants or a.mutation_scan or a.indel_scan or a.deletion_scan
-                                                    or a.shuffle_null):
+                                                    or a.substitution_scan or a.shuffle_null):
         sys.exit("ERROR: --affinity-temperature goes with --haplotype-affinity or --variant-affinity or --haplotype-classes")
     if a.affinity_temperature is not None and not a.affinity_temperature > 0:
         sys.exit(f"ERROR: --affinity-temperature {a.affinity_temperature} is not > 0")
@@ -327,7 +343,7 @@ def main(argv=None):
     _graph_only(a, "variant_affinity")
     if a.haplotype_groups and not (a.hit_alleles or a.hit_pairs or a.haplotype_classes or a.haplotype_sequences
                                    or a.query_variants or a.mutation_scan or a.indel_scan or a.deletion_scan
-                                   or a.shuffle_null):
+                                   or a.substitution_scan or a.shuffle_null):
         sys.exit("ERROR: --haplotype-groups goes with --hit-alleles or --hit-pairs or --haplotype-classes or "
                  "--haplotype-sequences")
     if a.class_min_haplotypes is not None and not a.haplotype_classes:
@@ -369,6 +385,25 @@ def main(argv=None):
             sys.exit(f"ERROR: --deletion-scan {bad[0]}: a length lies in 1 .. 64")
         a.deletion_scan = sorted(set(a.deletion_scan))
     _graph_only(a, "deletion_scan")
+    if a.substitution_all and not a.substitution_scan:
+        sys.exit("ERROR: --substitution-all goes with --substitution-scan")
+    if a.substitution_delta is not None and not a.substitution_scan:
+        sys.exit("ERROR: --substitution-delta goes with --substitution-scan")
+    if a.substitution_map is not None and not a.substitution_scan:
+        sys.exit("ERROR: --substitution-map goes with --substitution-scan")
+    if a.substitution_delta is not None and not a.substitution_delta >= 0:
+        sys.exit(f"ERROR: --substitution-delta {a.substitution_delta} is not >= 0")
+    if a.substitution_scan:
+        bad = [L for L in a.substitution_scan if not 1 <= L <= 64]
+        if bad:
+            sys.exit(f"ERROR: --substitution-scan {bad[0]}: a length lies in 1 .. 64")
+        a.substitution_scan = sorted(set(a.substitution_scan))
+        from .substitution_scan import checked_map
+        try:
+            checked_map(a.substitution_map or "transversion")
+        except ValueError as e:
+            sys.exit(f"ERROR: --substitution-map: {e}")
+    _graph_only(a, "substitution_scan")
     if a.null_seed is not None and a.shuffle_null is None:
         sys.exit("ERROR: --null-seed goes with --shuffle-null")
     if a.null_seed is not None and not 0 <= a.null_seed < 2**64:
@@ -602,6 +637,19 @@ def main(argv=None):
             for motif, t in zip(motifs, tables):
                 print(f"{len(t.summary_frame())} deletion scan summary rows written to "
                       f"{write_deletion_scan_summary(t, motif, len(motifs), wf)}")
+    if a.substitution_scan:
+        from .substitution_scan import (compute_substitution_scan_many, print_substitution_scan, write_substitution_scan,
+                                        write_substitution_scan_summary)
+        graph, regions, first_index = source("substitution_scan")
+        tables = compute_substitution_scan_many(motifs, graph, regions, a.debug, wf, a.substitution_scan,
+                                                a.substitution_map or "transversion", haplotype_groups=groups(first_index),
+                                                temperature=1.0 if a.affinity_temperature is None else a.affinity_temperature,
+                                                delta=a.substitution_delta, all_rows=a.substitution_all)
+        emit(tables, write_substitution_scan, print_substitution_scan, lambda t: f"{len(t)} substitution scan rows")
+        if not a.text_only:
+            for motif, t in zip(motifs, tables):
+                print(f"{len(t.summary_frame())} substitution scan summary rows written to "
+                      f"{write_substitution_scan_summary(t, motif, len(motifs), wf)}")
     if a.shuffle_null is not None:                     # (a table per motif, and one row per motif for the whole call)
         from .shuffle_null import (compute_shuffle_null_many, print_motif_enrichment, print_shuffle_null, write_motif_enrichment,
                                    write_shuffle_null)

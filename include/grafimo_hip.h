@@ -961,6 +961,43 @@ int gfm_sequence_deletion_scan(const gfm_motif_t *motifs, int32_t n_motifs, cons
                                const int32_t *lengths, uint32_t flags, uint32_t *const *d_keys, uint64_t *const *d_sums,
                                int32_t *d_status, void *stream);
 
+/* ------------------------------------------------------------------ substitution scan: every block of 1 .. 64 bases replaced in place by a base map
+ * Graph-independent.  THE RULE.  For a sequence x of n bases, a motif of width W, a strictly ascending list of lengths
+ * L0 < L1 < .. with every L in 1 .. GFM_SUBSCAN_MAX_LENGTH, a base map f given as four codes -- the images of A, C, G, T, each
+ * in 0 .. 3 for A, C, G, T; any map is allowed: fixed points, constant maps and the identity included --, every length L of
+ * the list and every offset o in 0 .. n - 1:
+ *   If o + L > n there is no edit: both keys and both sums of the cell are 0.
+ *   Otherwise y = x[:o] + f(x[o:o+L]) + x[o+L:].  f is applied base by base.  Case is folded, as base_code does.
+ *   A base that is not A/C/G/T maps to itself: unlike a deletion, a substituted N is NOT repaired.
+ *   This is gfm_graph_query_edits' rule with lr = la = L at offset o, the alleles not trimmed.
+ *     REF side (column COVER): the starts s of x with max(0, o - W + 1) <= s <= min(o + L - 1, n - W).  This is bit for bit the
+ *     deletion scan's COVER column.
+ *     ALT side (column SUB): the same starts in y.
+ *   Every window is scored once per strand, or + only under GFM_GRAPH_FORWARD_ONLY.
+ *   A window that holds a base that is not A/C/G/T scores min_val on both strands.
+ *   Per column, the best window by (score descending, s ascending, + before -), as the key
+ *   ((score + 1) << 8) | ((64 - (s - o)) << 1) | plus, s - o in -(W - 1) .. L - 1 on both sides: the values a
+ *   gfm_edit_record_t of the same edit holds.
+ *   Key 0 means the side has no window.
+ *   Per column, the exact uint64 sum of w[score] over the side's windows and strands.
+ *   Under the identity map SUB == COVER in every cell.
+ *   At L = 1, wherever x[o] is a base, SUB equals the mutation scan's column of the base f(x[o]), field for field.
+ * By construction a cell equals, field for field, what gfm_graph_query_edits returns for the edit (coordinate of o,
+ * x[o .. o + L - 1], f(x[o .. o + L - 1])) applied to x, wherever coordinates can name the block.
+ *
+ * The arguments, result shapes, alignment rules, refusals and the wait are gfm_sequence_deletion_scan's, with base_map, uint8
+ * [4] on the HOST, behind the lengths: base_map[i] is the image of "ACGT"[i] as an index into "ACGT".  d_keys[m] uint32
+ * [n_lengths][seq_offsets[n_seqs]][2], 8-byte aligned, and d_sums[m] uint64 of the same shape, 16-byte aligned: per length and
+ * base of d_bases the columns COVER, SUB.  Every cell is written, nothing is zeroed by the caller.  Refused when max_weight * 2 *
+ * (W + Lmax - 1) passes 2^64 - 1: either side has at most W + Lmax - 1 windows.  GFM_ERR_INVALID, all before anything is
+ * launched: what gfm_sequence_deletion_scan refuses, a NULL base_map, a code above 3.  The call WAITS for the stream. */
+#define GFM_SUBSCAN_TILE 64
+#define GFM_SUBSCAN_MAX_LENGTH 64
+int gfm_sequence_substitution_scan(const gfm_motif_t *motifs, int32_t n_motifs, const uint64_t *const *d_weights,
+                                   uint64_t max_weight, int32_t n_seqs, const int64_t *seq_offsets, const uint8_t *d_bases,
+                                   int32_t n_lengths, const int32_t *lengths, const uint8_t base_map[4], uint32_t flags,
+                                   uint32_t *const *d_keys, uint64_t *const *d_sums, int32_t *d_status, void *stream);
+
 /* ------------------------------------------------------------------ shuffle null: empirical p-values for best score and total affinity
  * Graph-independent.  THE RULE.  All arithmetic on 64-bit words is modulo 2^64.
  *   G = 0x9E3779B97F4A7C15.

@@ -1,0 +1,156 @@
+"""What the substitution scan costs, beside the only way the tree could produce its numbers before: --seqs random sequences of
+--length bases (the other sequence probes' 2 000 x 300), every base non-inserted with consecutive coordinates, so that every
+block that fits its sequence is one a coordinate can name; three synthetic motifs of W = 19; the map CATG (the transversion).
+Reported for the lengths (1,), (5, 10, 20) and (64,):
+  the new entry   gfm_sequence_substitution_scan over the staged sequences and reused result tensors;
+  the baseline    gfm_graph_query_edits (query_variants.score_edits' entry) over the SAME sequences with one item per (offset,
+                  length) whose block fits -- exactly the substitutions the new entry scores, REF the block and ALT its image,
+                  untrimmed --, staged once, a reused record tensor;
+  the sibling     gfm_sequence_deletion_scan on the same input and lengths, whose COVER column is the same and whose ALT side
+                  has W - 1 windows a cell where the substitution's has W + L - 1;
+each with two hipEvents on the stream around the entry, --warmup passes, then --reps timed ones, median / min / max (each entry
+clears a word, launches, copies 4 bytes back and waits for the stream: the figure is the kernels plus some tens of
+microseconds), the ratio of the medians, whether the slowest pass of the new entry is below the fastest of the baseline (the
+run-to-run spread the probe itself sees), and whether the two agree field for field on every item (compared on the device).
+
+    python scripts/substitution_scan_probe.py [--seqs 2000] [--length 300] [--reps 10] [--warmup 3] [--out FILE]
+"""
+import argparse
+import ctypes
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def _timed(run, warmup, reps):
+    import torch
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+    ms = []
+    for rep in range(warmup + reps):
+        torch.cuda.synchronize()
+        ev[0].record()
+        run()
+        ev[1].record()
+        torch.cuda.synchronize()
+        if rep >= warmup:
+            ms.append(ev[0].elapsed_time(ev[1]))
+    return statistics.median(ms), min(ms), max(ms)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--seqs", type=int, default=2000)
+    ap.add_argument("--length", type=int, default=300)
+    ap.add_argument("--reps", type=int, default=10)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    import numpy as np
+    import torch
+    from grafimo_amd import _native as nv
+    from grafimo_amd import deletion_scan as dsc
+    from grafimo_amd import query_variants as qv
+    from grafimo_amd import substitution_scan as ssc
+    from grafimo_amd import synth
+    from grafimo_amd.device import DeviceMotif
+    from grafimo_amd.extract_regions import _stream_ptr
+
+    W, n_motifs, letters = 19, 3, "CATG"
+    rng = np.random.default_rng(23)
+    V, n = a.seqs, a.length
+    N = V * n
+    bases = np.frombuffer(b"ACGT", dtype=np.uint8)[rng.integers(0, 4, size=N)]
+    images = ssc.mapped_bases(bases, letters)
+    base_map = ssc.checked_map(letters)
+    seq_offsets = np.arange(V + 1, dtype=np.int64) * n
+    within = np.tile(np.arange(n, dtype=np.int64), V)
+    coord = within.astype(np.int32)                               # every sequence carries the coordinates 0 .. n - 1
+    dev = torch.device("cuda", torch.cuda.current_device())
+    up = lambda x, dt: torch.from_numpy(np.ascontiguousarray(x, dtype=dt)).to(dev)      # noqa: E731
+    lines = [f"input: {V} sequences of {n} bases = {N} bases, none inserted; {n_motifs} motifs of W = {W}; map {letters}; "
+             f"{torch.cuda.get_device_name(0)}"]
+    motifs = [synth.motif_object(synth.synthetic_motif(W, np.random.default_rng(7 + k), np.full(4, 0.25)), f"P{W}_{k}")
+              for k in range(n_motifs)]
+    dms = [DeviceMotif.lease(m) for m in motifs]
+    tables, _ = qv._weight_tables(dms, motifs, None, 1.0)
+    d_tabs = [up(t.view(np.int64), np.int64) for t in tables]
+    max_weight = max(int(t.max()) for t in tables)
+    d_bases = up(bases, np.uint8)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    vp = ctypes.c_void_p
+    handles, tabs = (vp * n_motifs)(*[x.handle for x in dms]), (vp * n_motifs)(*[t.data_ptr() for t in d_tabs])
+    ok = True
+    for lengths in ((1,), (5, 10, 20), (64,)):
+        ln = dsc.checked_lengths(lengths)
+        K = len(ln)
+        keys = torch.empty((n_motifs, K, N, 2), dtype=torch.int32, device=dev)
+        sums = torch.empty((n_motifs, K, N, 2), dtype=torch.int64, device=dev)
+        kp = (vp * n_motifs)(*[keys[m].data_ptr() for m in range(n_motifs)])
+        sp = (vp * n_motifs)(*[sums[m].data_ptr() for m in range(n_motifs)])
+        new = _timed(lambda: nv.check(getattr(nv.lib(), ssc.ENTRY)(handles, n_motifs, tabs, max_weight, V, seq_offsets.ctypes.data,
+                                                                 d_bases.data_ptr(), K, ln.ctypes.data, base_map.ctypes.data, 0, kp, sp,
+                                                                 status.data_ptr(), _stream_ptr(None))), a.warmup, a.reps)
+        # ---- the baseline: an edit and an item per (length, base) whose block fits, in that order
+        cell_k, cell_n, ref_bytes, alt_bytes, ref_len = [], [], [], [], []
+        for k, L in enumerate(lengths):
+            at = np.flatnonzero(within + L <= n)
+            cell_k.append(np.full(len(at), k, dtype=np.int64))
+            cell_n.append(at)
+            block = at[:, None] + np.arange(L, dtype=np.int64)[None, :]
+            ref_bytes.append(bases[block].reshape(-1))
+            alt_bytes.append(images[block].reshape(-1))
+            ref_len.append(np.full(len(at), L, dtype=np.int64))
+        cell_k, cell_n, ref_len = np.concatenate(cell_k), np.concatenate(cell_n), np.concatenate(ref_len)
+        Q = len(cell_n)
+        ref_off = np.concatenate([[0], np.cumsum(ref_len)])
+        assert int(ref_off[-1]) < 1 << 31
+        d_off = up(ref_off, np.int32)                             # (an ALT is as long as its REF)
+        d_edits = [up(seq_offsets, np.int64), d_bases, up(coord, np.int32), up(within[cell_n], np.int64), d_off,
+                   up(np.concatenate(ref_bytes), np.uint8), d_off, up(np.concatenate(alt_bytes), np.uint8),
+                   up(cell_n // n, np.int32), up(np.arange(Q), np.int32)]
+        q_staged = (d_edits, d_tabs, max_weight, (V, Q, Q))
+        rec = torch.zeros((n_motifs, Q, 4), dtype=torch.int64, device=dev)
+        old = _timed(lambda: qv._enqueue(dms, q_staged, False, rec), a.warmup, a.reps)
+        # ---- field for field: status applied in the low word and o above it, the keys packed, the sums
+        cell = up((cell_k * N + cell_n) * 2, np.int64)
+        fk, fs = keys.view(n_motifs, -1), sums.view(n_motifs, -1)
+        same = bool((rec[:, :, 0] == up(within[cell_n] << 32, np.int64)[None, :]).all())
+        same &= bool((rec[:, :, 2] == fs[:, cell]).all()) and bool((rec[:, :, 3] == fs[:, cell + 1]).all())
+        packed = (fk[:, cell].to(torch.int64) & 0xffffffff) | ((fk[:, cell + 1].to(torch.int64) & 0xffffffff) << 32)
+        same &= bool((rec[:, :, 1] == packed).all())
+        below = new[2] < old[1]
+        ok &= same and below
+        lines.append(f"lengths {tuple(lengths)}: gfm_sequence_substitution_scan over {N} bases: median {new[0]:.3f} ms (min {new[1]:.3f}, "
+                     f"max {new[2]:.3f}); gfm_graph_query_edits over the same {Q} substitutions: median {old[0]:.3f} ms (min "
+                     f"{old[1]:.3f}, max {old[2]:.3f}); {a.warmup} warm-ups, {a.reps} timed; ratio {old[0] / new[0]:.1f}x; the new "
+                     f"entry's slowest pass is below the baseline's fastest: {below}; {Q * n_motifs / new[0] / 1e6:.3f} G "
+                     f"substitutions/s; the two agree on every item: {same}")
+        del rec, q_staged, d_edits
+        # ---- the sibling: the deletion scan on the same input, into tensors of its own
+        dkeys, dsums = torch.empty_like(keys), torch.empty_like(sums)
+        dkp = (vp * n_motifs)(*[dkeys[m].data_ptr() for m in range(n_motifs)])
+        dsp = (vp * n_motifs)(*[dsums[m].data_ptr() for m in range(n_motifs)])
+        sib = _timed(lambda: nv.check(getattr(nv.lib(), dsc.ENTRY)(handles, n_motifs, tabs, max_weight, V, seq_offsets.ctypes.data,
+                                                                 d_bases.data_ptr(), K, ln.ctypes.data, 0, dkp, dsp, status.data_ptr(),
+                                                                 _stream_ptr(None))), a.warmup, a.reps)
+        equal = bool((dkeys[..., 0] == keys[..., 0]).all()) and bool((dsums[..., 0] == sums[..., 0]).all())
+        ok &= equal
+        lines.append(f"lengths {tuple(lengths)}: gfm_sequence_deletion_scan on the same input: median {sib[0]:.3f} ms (min {sib[1]:.3f}, "
+                     f"max {sib[2]:.3f}); the substitution scan takes {new[0] / sib[0]:.2f}x its time; the COVER columns are equal: "
+                     f"{equal}")
+        del keys, sums, dkeys, dsums
+    for dm in dms:
+        dm.release()
+    text = "\n".join(lines)
+    print(text)
+    if a.out:
+        with open(a.out, "w") as fh:
+            fh.write(text + "\n")
+    return 0 if ok else 1
+
+
+if __name__ == "__main__":
+    sys.exit(main())
