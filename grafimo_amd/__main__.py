@@ -124,7 +124,7 @@ def get_parser():
                    help="also write grafimo_hit_alleles[_MOTIF].tsv (printed with -f): the report's rows, each with the variant "
                         "alleles that make its k-mer and, with --haplotype-groups, its carriers per group (graph routes only)")
     p.add_argument("--haplotype-groups", dest="haplotype_groups", metavar="FILE",
-                   help="with --hit-alleles, --hit-pairs, --haplotype-classes, --haplotype-sequences, --query-variants, --mutation-scan, --indel-scan, --deletion-scan, --substitution-scan or --shuffle-null: SAMPLE GROUP lines (the 1000 Genomes panel file reads as is), one "
+                   help="with --hit-alleles, --hit-pairs, --haplotype-classes, --haplotype-sequences, --query-variants, --mutation-scan, --indel-scan, --deletion-scan, --substitution-scan, --site-distance or --shuffle-null: SAMPLE GROUP lines (the 1000 Genomes panel file reads as is), one "
                         "haplotypes_GROUP column per group")
     p.add_argument("--haplotype-classes", action="store_true", dest="haplotype_classes",
                    help="also write grafimo_haplotype_classes[_MOTIF].tsv (printed with -f) and "
@@ -197,6 +197,15 @@ def get_parser():
                    help="with --substitution-scan: also keep the rows with |delta_log2_affinity| >= X")
     p.add_argument("--substitution-all", action="store_true", dest="substitution_all",
                    help="with --substitution-scan: keep every row, up to one per base and length")
+    p.add_argument("--site-distance", dest="site_distance", nargs="?", type=int, const=3, default=None, metavar="E",
+                   help="also write grafimo_site_distance[_MOTIF].tsv and grafimo_site_distance_summary[_MOTIF].tsv (printed "
+                        "with -f): for every window of every sequence the haplotypes spell in a region (inserted bases too) and "
+                        "of the reference sequence, on both strands, the least number of substitutions, up to E in 1 .. 8 "
+                        "(default 3), that lifts it to a hit at p < -t, or that drops a hit under it, with the changes and the "
+                        "edited k-mer, and per coordinate the haplotypes with a site, with a near-site at each distance, in "
+                        "all and per --haplotype-groups group; rows are kept for sites and near-sites (graph routes only)")
+    p.add_argument("--site-distance-all", action="store_true", dest="site_distance_all",
+                   help="with --site-distance: keep every window and strand, also those more than E substitutions from a site")
     p.add_argument("--shuffle-null", dest="shuffle_null", nargs="?", type=int, const=1000, default=None, metavar="K",
                    help="also write grafimo_shuffle_null[_MOTIF].tsv and grafimo_motif_enrichment.tsv (printed with -f): every "
                         "sequence the haplotypes spell in a region, and the reference sequence, against K (default 1000) "
@@ -290,7 +299,7 @@ _GRAPH_TABLES = {"variant_effects": ("--variant-effects", "alleles"), "haplotype
                  "haplotype_sequences": ("--haplotype-sequences", "haplotypes"),
                  "query_variants": ("--query-variants", "haplotypes"), "mutation_scan": ("--mutation-scan", "haplotypes"),
                  "indel_scan": ("--indel-scan", "haplotypes"), "deletion_scan": ("--deletion-scan", "haplotypes"),
-                 "substitution_scan": ("--substitution-scan", "haplotypes"),
+                 "substitution_scan": ("--substitution-scan", "haplotypes"), "site_distance": ("--site-distance", "haplotypes"),
                  "shuffle_null": ("--shuffle-null", "haplotypes")}
 
 
@@ -343,9 +352,9 @@ def main(argv=None):
     _graph_only(a, "variant_affinity")
     if a.haplotype_groups and not (a.hit_alleles or a.hit_pairs or a.haplotype_classes or a.haplotype_sequences
                                    or a.query_variants or a.mutation_scan or a.indel_scan or a.deletion_scan
-                                   or a.substitution_scan or a.shuffle_null):
+                                   or a.substitution_scan or a.site_distance or a.shuffle_null):
         sys.exit("ERROR: --haplotype-groups goes with --hit-alleles or --hit-pairs or --haplotype-classes or "
-                 "--haplotype-sequences")
+                 "--haplotype-sequences or --site-distance")
     if a.class_min_haplotypes is not None and not a.haplotype_classes:
         sys.exit("ERROR: --class-min-haplotypes goes with --haplotype-classes")
     if a.class_min_haplotypes is not None and a.class_min_haplotypes < 1:
@@ -404,6 +413,11 @@ def main(argv=None):
         except ValueError as e:
             sys.exit(f"ERROR: --substitution-map: {e}")
     _graph_only(a, "substitution_scan")
+    if a.site_distance_all and a.site_distance is None:
+        sys.exit("ERROR: --site-distance-all goes with --site-distance")
+    if a.site_distance is not None and not 1 <= a.site_distance <= 8:
+        sys.exit(f"ERROR: --site-distance {a.site_distance}: the number of substitutions lies in 1 .. 8")
+    _graph_only(a, "site_distance")
     if a.null_seed is not None and a.shuffle_null is None:
         sys.exit("ERROR: --null-seed goes with --shuffle-null")
     if a.null_seed is not None and not 0 <= a.null_seed < 2**64:
@@ -650,6 +664,17 @@ def main(argv=None):
             for motif, t in zip(motifs, tables):
                 print(f"{len(t.summary_frame())} substitution scan summary rows written to "
                       f"{write_substitution_scan_summary(t, motif, len(motifs), wf)}")
+    if a.site_distance is not None:
+        from .site_distance import (compute_site_distance_many, print_site_distance, write_site_distance,
+                                    write_site_distance_summary)
+        graph, regions, first_index = source("site_distance")
+        tables = compute_site_distance_many(motifs, graph, regions, a.debug, wf, haplotype_groups=groups(first_index),
+                                            max_edits=a.site_distance, all_rows=a.site_distance_all)
+        emit(tables, write_site_distance, print_site_distance, lambda t: f"{len(t)} site distance rows")
+        if not a.text_only:
+            for motif, t in zip(motifs, tables):
+                print(f"{len(t.summary_frame())} site distance summary rows written to "
+                      f"{write_site_distance_summary(t, motif, len(motifs), wf)}")
     if a.shuffle_null is not None:                     # (a table per motif, and one row per motif for the whole call)
         from .shuffle_null import (compute_shuffle_null_many, print_motif_enrichment, print_shuffle_null, write_motif_enrichment,
                                    write_shuffle_null)

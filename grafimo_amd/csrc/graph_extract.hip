@@ -2648,4 +2648,5 @@ inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 #include "gfm_graph_indel_scan.hpp"
 #include "gfm_graph_deletion_scan.hpp"
 #include "gfm_graph_substitution_scan.hpp"
+#include "gfm_graph_site_distance.hpp"
 #include "gfm_graph_shuffle_null.hpp"

@@ -998,6 +998,57 @@ int gfm_sequence_substitution_scan(const gfm_motif_t *motifs, int32_t n_motifs, 
                                    int32_t n_lengths, const int32_t *lengths, const uint8_t base_map[4], uint32_t flags,
                                    uint32_t *const *d_keys, uint64_t *const *d_sums, int32_t *d_status, void *stream);
 
+/* ------------------------------------------------------------------ site distance: substitutions from a site, for every window of a spelled sequence
+ * Graph-independent.  THE RULE.
+ * Inputs: a sequence x of n bases; a motif of width W with its integer matrix as the packed table holds it, entry t[j][b] for
+ * the window's forward column j and base b, one table per strand; a cutoff c in 0 .. 1000 W + 1; a cap E in 1 .. 8.
+ * Every window start s in 0 .. n - W and every strand is handled independently.
+ * Under GFM_GRAPH_FORWARD_ONLY only the + strand is handled.  Case is folded, as base_code does.
+ * A window that holds a column with no A/C/G/T scores min_val on both strands.  Otherwise its score is the sum of its entries.
+ * A window's unedited score on a strand is its `own` score.  The window is a site on that strand when own >= c.
+ * Raising (the near side).  Start from the window as spelled and repeat these steps:
+ *   1. If the current score >= c, stop with d = picks made.
+ *   2. If E picks are made, stop with d = E + 1.
+ *   3. If a non-base column remains, the next pick is the leftmost such column.  It gets the column's best base: the largest
+ *      entry on this strand.  Ties go to the first of A, C, G, T.  While any non-base column remains, the score stays min_val.
+ *   4. Otherwise the next pick is the unpicked base column with the largest gain.  The gain is the column's largest entry minus
+ *      its present entry.  Ties go to the leftmost column.  The column gets that best base.  Ties go to the first of A, C, G, T.
+ *   5. If every remaining gain is 0, stop with d = E + 1.
+ * Lowering (the fragile side).
+ *   1. If own < c, d = 0 and there are no picks.
+ *   2. A window with a non-base column takes no picks: d = 0 if min_val < c, otherwise d = E + 1.
+ *   3. Otherwise pick as above, with the loss in place of the gain.  The loss is the present entry minus the column's smallest
+ *      entry.  The worst base is the smallest entry.  Ties go to the first of A, C, G, T.  Stop when the score < c, with d = picks
+ *      made.  Stop at E picks, or when every remaining loss is 0, with d = E + 1.
+ * Results per (window start, strand, side): d in 0 .. E + 1; the score after the picks made; the 64-bit mask of the picked
+ * forward columns, bit j for column j.  d and the score do not depend on the tie rules.  Only the mask does.
+ * By the exchange argument d is the true minimum whenever it is <= E.
+ * Columns are always forward offsets in the window.  Bases are forward-strand bases.  The - strand reads its own half of the
+ * packed table at the same forward column.
+ *
+ * n_motifs motifs of ONE width on the current device.  seq_offsets: HOST, int64 [n_seqs + 1], ascending from seq_offsets[0] >= 0:
+ * the bases of sequence v are d_bases[seq_offsets[v] .. seq_offsets[v + 1]); empty sequences are allowed.  cutoffs: HOST, int32
+ * [n_motifs], the cutoff c of every motif.  max_edits: the cap E in 1 .. GFM_SITEDIST_MAX_EDITS.  Per motif and per base n of
+ * d_bases, read as a window start:
+ *   d_words[m] uint32 [seq_offsets[n_seqs]][6] = own +, own -, near +, near -, fragile +, fragile -.  An own word is the score.
+ *   A near or fragile word is (score_after << 4) | d.  0xFFFFFFFF in any column means "no window": a start beyond n - W, or the
+ *   - columns under GFM_GRAPH_FORWARD_ONLY.
+ *   d_masks[m] uint64 [seq_offsets[n_seqs]][4], 8-byte aligned = near +, near -, fragile +, fragile -: 0 where there is no window.
+ * Every row of both arrays is written, nothing is zeroed by the caller.  d_status int32: a device word of the caller's, cleared
+ * and read here.  The work is cut into (sequence, GFM_SITEDIST_TILE window starts) tiles by the library; the result does not
+ * depend on the tile -- it is exported only so that tests can aim at its edges.  No sequence or no base returns GFM_OK and
+ * touches nothing, after the checks.  GFM_ERR_INVALID, all before anything is launched and also when there is no sequence:
+ * n_motifs < 1, n_seqs < 0, an unknown flag, max_edits outside 1 .. GFM_SITEDIST_MAX_EDITS, NULL cutoffs, a cutoff that no width
+ * allows, offsets that descend, a sequence of 2^31 bases or more; with bases, a NULL pointer or a misaligned d_masks[m];
+ * wherever motifs are given, motifs of different widths or on another device than the current one, a width outside [1, 64], a
+ * cutoff outside 0 .. 1000 W + 1.  The call WAITS for the stream (it reads the verdict of the device's check of the tile
+ * table). */
+#define GFM_SITEDIST_TILE 64
+#define GFM_SITEDIST_MAX_EDITS 8
+int gfm_sequence_site_distance(const gfm_motif_t *motifs, int32_t n_motifs, int32_t n_seqs, const int64_t *seq_offsets,
+                               const uint8_t *d_bases, const int32_t *cutoffs, int32_t max_edits, uint32_t flags,
+                               uint32_t *const *d_words, uint64_t *const *d_masks, int32_t *d_status, void *stream);
+
 /* ------------------------------------------------------------------ shuffle null: empirical p-values for best score and total affinity
  * Graph-independent.  THE RULE.  All arithmetic on 64-bit words is modulo 2^64.
  *   G = 0x9E3779B97F4A7C15.
