@@ -23,6 +23,7 @@ substitutions, insertions and deletions of the VCF are part of that graph (grafi
     python -m grafimo_amd -m MA0139.1.meme -l chr22.fa -v chr22.vcf.gz -b peaks.bed -o out_dir
 """
 import argparse
+import importlib
 import sys
 import time
 
@@ -616,65 +617,31 @@ def main(argv=None):
             for motif, t in zip(motifs, tables):
                 print(f"{len(t.contexts_frame())} query variant context rows written to "
                       f"{write_query_variant_contexts(t, motif, len(motifs), wf)}")
-    if a.mutation_scan:
-        from .mutation_scan import (compute_mutation_scan_many, print_mutation_scan, write_mutation_scan,
-                                    write_mutation_scan_summary)
-        graph, regions, first_index = source("mutation_scan")
-        tables = compute_mutation_scan_many(motifs, graph, regions, a.debug, wf, haplotype_groups=groups(first_index),
-                                            temperature=1.0 if a.affinity_temperature is None else a.affinity_temperature,
-                                            delta=a.mutation_delta, all_rows=a.mutation_all)
-        emit(tables, write_mutation_scan, print_mutation_scan, lambda t: f"{len(t)} mutation scan rows")
+    # the sequence scans: (asked for, the module's and the source's name, the noun of the printed lines, what
+    # compute_<name>_many takes beyond the shared arguments)
+    temperature = 1.0 if a.affinity_temperature is None else a.affinity_temperature
+    for asked, name, noun, positional, named in (
+            (a.mutation_scan, "mutation_scan", "mutation scan", (),
+             dict(temperature=temperature, delta=a.mutation_delta, all_rows=a.mutation_all)),
+            (a.indel_scan, "indel_scan", "indel scan", (),
+             dict(temperature=temperature, delta=a.indel_delta, all_rows=a.indel_all)),
+            (a.deletion_scan, "deletion_scan", "deletion scan", (a.deletion_scan,),
+             dict(temperature=temperature, delta=a.deletion_delta, all_rows=a.deletion_all)),
+            (a.substitution_scan, "substitution_scan", "substitution scan", (a.substitution_scan, a.substitution_map or "transversion"),
+             dict(temperature=temperature, delta=a.substitution_delta, all_rows=a.substitution_all)),
+            (a.site_distance is not None, "site_distance", "site distance", (),
+             dict(max_edits=a.site_distance, all_rows=a.site_distance_all))):
+        if not asked:
+            continue
+        module = importlib.import_module(f".{name}", __package__)
+        compute, write, write_summary, show = (getattr(module, f"compute_{name}_many"), getattr(module, f"write_{name}"),
+                                               getattr(module, f"write_{name}_summary"), getattr(module, f"print_{name}"))
+        graph, regions, first_index = source(name)
+        tables = compute(motifs, graph, regions, a.debug, wf, *positional, haplotype_groups=groups(first_index), **named)
+        emit(tables, write, show, lambda t: f"{len(t)} {noun} rows")
         if not a.text_only:
             for motif, t in zip(motifs, tables):
-                print(f"{len(t.summary_frame())} mutation scan summary rows written to "
-                      f"{write_mutation_scan_summary(t, motif, len(motifs), wf)}")
-    if a.indel_scan:
-        from .indel_scan import compute_indel_scan_many, print_indel_scan, write_indel_scan, write_indel_scan_summary
-        graph, regions, first_index = source("indel_scan")
-        tables = compute_indel_scan_many(motifs, graph, regions, a.debug, wf, haplotype_groups=groups(first_index),
-                                         temperature=1.0 if a.affinity_temperature is None else a.affinity_temperature,
-                                         delta=a.indel_delta, all_rows=a.indel_all)
-        emit(tables, write_indel_scan, print_indel_scan, lambda t: f"{len(t)} indel scan rows")
-        if not a.text_only:
-            for motif, t in zip(motifs, tables):
-                print(f"{len(t.summary_frame())} indel scan summary rows written to "
-                      f"{write_indel_scan_summary(t, motif, len(motifs), wf)}")
-    if a.deletion_scan:
-        from .deletion_scan import (compute_deletion_scan_many, print_deletion_scan, write_deletion_scan,
-                                    write_deletion_scan_summary)
-        graph, regions, first_index = source("deletion_scan")
-        tables = compute_deletion_scan_many(motifs, graph, regions, a.debug, wf, a.deletion_scan, haplotype_groups=groups(first_index),
-                                            temperature=1.0 if a.affinity_temperature is None else a.affinity_temperature,
-                                            delta=a.deletion_delta, all_rows=a.deletion_all)
-        emit(tables, write_deletion_scan, print_deletion_scan, lambda t: f"{len(t)} deletion scan rows")
-        if not a.text_only:
-            for motif, t in zip(motifs, tables):
-                print(f"{len(t.summary_frame())} deletion scan summary rows written to "
-                      f"{write_deletion_scan_summary(t, motif, len(motifs), wf)}")
-    if a.substitution_scan:
-        from .substitution_scan import (compute_substitution_scan_many, print_substitution_scan, write_substitution_scan,
-                                        write_substitution_scan_summary)
-        graph, regions, first_index = source("substitution_scan")
-        tables = compute_substitution_scan_many(motifs, graph, regions, a.debug, wf, a.substitution_scan,
-                                                a.substitution_map or "transversion", haplotype_groups=groups(first_index),
-                                                temperature=1.0 if a.affinity_temperature is None else a.affinity_temperature,
-                                                delta=a.substitution_delta, all_rows=a.substitution_all)
-        emit(tables, write_substitution_scan, print_substitution_scan, lambda t: f"{len(t)} substitution scan rows")
-        if not a.text_only:
-            for motif, t in zip(motifs, tables):
-                print(f"{len(t.summary_frame())} substitution scan summary rows written to "
-                      f"{write_substitution_scan_summary(t, motif, len(motifs), wf)}")
-    if a.site_distance is not None:
-        from .site_distance import (compute_site_distance_many, print_site_distance, write_site_distance,
-                                    write_site_distance_summary)
-        graph, regions, first_index = source("site_distance")
-        tables = compute_site_distance_many(motifs, graph, regions, a.debug, wf, haplotype_groups=groups(first_index),
-                                            max_edits=a.site_distance, all_rows=a.site_distance_all)
-        emit(tables, write_site_distance, print_site_distance, lambda t: f"{len(t)} site distance rows")
-        if not a.text_only:
-            for motif, t in zip(motifs, tables):
-                print(f"{len(t.summary_frame())} site distance summary rows written to "
-                      f"{write_site_distance_summary(t, motif, len(motifs), wf)}")
+                print(f"{len(t.summary_frame())} {noun} summary rows written to {write_summary(t, motif, len(motifs), wf)}")
     if a.shuffle_null is not None:                     # (a table per motif, and one row per motif for the whole call)
         from .shuffle_null import (compute_shuffle_null_many, print_motif_enrichment, print_shuffle_null, write_motif_enrichment,
                                    write_shuffle_null)

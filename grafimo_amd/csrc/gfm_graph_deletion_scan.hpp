@@ -1,8 +1,9 @@
 // gfm_graph_deletion_scan.hpp -- deletion scan: the deletion of every block of L bases of a spelled sequence, for a list of
 // lengths L in 1 .. GFM_DELSCAN_MAX_LENGTH, every window the edit touches scored before and after on both strands (included at
-// the end of graph_extract.hip behind gfm_graph_indel_scan.hpp, whose bits_from and indel_stride it shares, with
-// gfm_graph_mutation_scan.hpp's MsTile, kMsBadTile and kMsMaxBlocks; it uses base_code, view_motif_set, SeqMotifs, GX_TRY,
-// gfail, align256 and gfm_graph_table_score.hpp's strand_scores, walk_value and edit_key).  It is the indel-scan kernel's
+// the end of graph_extract.hip behind gfm_graph_indel_scan.hpp, whose bits_from and indel_stride it shares;
+// gfm_sequence_tiles.hpp gives it SeqTile, CellResults, SideBest, the COVER walk (cover_head, cover_extend), the tile check, the
+// table staging, the length mask, seq_sum_fits and the host protocol; it uses base_code, view_motif_set, SeqMotifs, gfail and
+// gfm_graph_table_score.hpp's strand_scores and walk_value).  It is the indel-scan kernel's
 // deletion half stretched by the longest length: every window start is scored ONCE, the running prefixes of that pass are
 // kept, and every junction window of every deletion is put together from two stored pieces.
 //
@@ -69,18 +70,13 @@ __host__ __device__ constexpr size_t delscan_lds_bytes(int W, int lmax)
 __host__ constexpr unsigned delscan_side_windows(int W, int lmax) { return 2u * (unsigned)(W + lmax - 1); }
 __host__ constexpr bool delscan_sum_fits(uint64_t max_weight, int W, int lmax)
 {
-    return (unsigned __int128)max_weight * delscan_side_windows(W, lmax) <= (unsigned __int128)UINT64_MAX;
+    return seq_sum_fits(max_weight, delscan_side_windows(W, lmax));
 }
 static_assert(delscan_sum_fits(UINT64_MAX / 254u, 64, 64) && !delscan_sum_fits(UINT64_MAX / 254u + 1u, 64, 64), "the bound is exact");
 
-struct DsResults {
-    uint2 *keys[kSeqMotifs];                                      // [n_lengths][n_bases] (COVER, DEL)
-    ulonglong2 *sums[kSeqMotifs];
-};
-
 __global__ void __launch_bounds__(kDsThreads)
-deletion_scan_kernel(const MsTile *__restrict__ tiles, long long n_tiles, const uint8_t *__restrict__ bases, long long n_bases,
-                     SeqMotifs mt, DsResults res, int W, unsigned long long lengths, int forward_only, int *__restrict__ status)
+deletion_scan_kernel(const SeqTile *__restrict__ tiles, long long n_tiles, const uint8_t *__restrict__ bases, long long n_bases,
+                     SeqMotifs mt, CellResults res, int W, unsigned long long lengths, int forward_only, int *__restrict__ status)
 {
     extern __shared__ unsigned a_s[];                             // A(lo + row, m) at [row * stride + m - 1], m = 1 .. W
     __shared__ unsigned ftab_s[GFM_MAX_WIDTH * 8];
@@ -89,7 +85,7 @@ deletion_scan_kernel(const MsTile *__restrict__ tiles, long long n_tiles, const 
     __shared__ unsigned wsc_s[kDsWindows];                        // + score | - score << 16, under the non-base rule
     __shared__ unsigned char code_s[kDsCodes];
     const int mi = blockIdx.y, tid = threadIdx.x;
-    for (int i = tid; i < W * 8; i += kDsThreads) ftab_s[i] = mt.ftab[mi][i];
+    stage_table(ftab_s, mt.ftab[mi], W, kDsThreads);
     const unsigned long long *__restrict__ wtab = mt.wtab[mi];
     uint2 *__restrict__ keys = res.keys[mi];
     ulonglong2 *__restrict__ sums = res.sums[mi];
@@ -97,12 +93,8 @@ deletion_scan_kernel(const MsTile *__restrict__ tiles, long long n_tiles, const 
     const int stride = indel_stride(W);
     const int lmax = lengths ? 64 - __builtin_clzll(lengths) : 0;
     for (long long t = blockIdx.x; t < n_tiles; t += gridDim.x) {
-        const MsTile tile = tiles[t];
-        // ---- the tile, checked: everything read and written below lies inside its sequence (uniform: no thread stays behind)
-        if (tile.begin < 0 || tile.len <= 0 || tile.begin > n_bases - tile.len || tile.start < 0 || tile.start >= tile.len) {
-            if (tid == 0) atomicOr(status, kMsBadTile);
-            continue;
-        }
+        const SeqTile tile = tiles[t];
+        if (seq_tile_bad(tile, n_bases, status)) continue;
         const uint8_t *__restrict__ x = bases + tile.begin;
         const int len = tile.len, lo = tile.start, nt = min(kDsTile, len - lo);
         __syncthreads();                                          // (the table is staged; the last tile's rows are read)
@@ -143,34 +135,17 @@ deletion_scan_kernel(const MsTile *__restrict__ tiles, long long n_tiles, const 
             const int dl = before ? __builtin_clzll(before) : 64;
             const unsigned *a_o = a_s + tid * stride;             // A(o, m) = a_o[m - 1]
             const int last_start = len - W;                       // the last window start of x
-            unsigned key_c = 0u;
-            unsigned long long sum_c = 0ull;
-            // COVER's part every length shares: the starts o - m, m = W - 1 .. 1
-            for (int m = min(W - 1, o); m >= 1; --m) {
-                if (o - m > last_start) continue;
-                const int k = tid + W - 1 - m;
-                const unsigned sc = wsc_s[k];
-                key_c = max(key_c, edit_key((int)(sc & 0xffffu), -m, true));
-                if (!forward_only) key_c = max(key_c, edit_key((int)(sc >> 16), -m, false));
-                sum_c += wref_s[k];
-            }
+            SideBest cover;
+            cover_head(cover, wsc_s, wref_s, tid, W, o, last_start, forward_only);
             int l_prev = 0;
             long long cell = tile.begin + o;                      // of the first listed length; the next is n_bases further
             for (unsigned long long rest = lengths; rest; rest &= rest - 1ull, cell += n_bases) {
                 const int L = __builtin_ctzll(rest) + 1;
                 if (o + L > len) {                                // no edit (and none at any longer length)
-                    keys[cell] = make_uint2(0u, 0u);
-                    sums[cell] = make_ulonglong2(0ull, 0ull);
+                    store_cell(keys, sums, cell, SideBest{}, SideBest{});
                     continue;
                 }
-                // COVER: the starts o + l_prev .. o + L - 1 are new
-                for (int d = l_prev; d < L && o + d <= last_start; ++d) {
-                    const int k = tid + W - 1 + d;
-                    const unsigned sc = wsc_s[k];
-                    key_c = max(key_c, edit_key((int)(sc & 0xffffu), d, true));
-                    if (!forward_only) key_c = max(key_c, edit_key((int)(sc >> 16), d, false));
-                    sum_c += wref_s[k];
-                }
+                cover_extend(cover, wsc_s, wref_s, tid, W, o, last_start, l_prev, L, forward_only);
                 l_prev = L;
                 // DEL: the junction window m starts at o - m and ends W - m bases behind the block
                 const int g = tid + 64 + L;                       // the bitmap's bit of position o + L: 65 .. 191
@@ -180,17 +155,12 @@ deletion_scan_kernel(const MsTile *__restrict__ tiles, long long n_tiles, const 
                 const int r = len - L - o;                        // the bases behind the block
                 const unsigned *a_l = a_o + L * stride;           // A(o + L, m) = a_l[m - 1]
                 const unsigned *full_l = wsum_s + (tid + L + W - 1);                 // Full[o + L - m] = full_l[-m]
-                unsigned key_d = 0u;
-                unsigned long long sum_d = 0ull;
+                SideBest del;
                 for (int m = max(1, W - r); m <= min(W - 1, o); ++m) {
                     const WindowSum w{a_o[m - 1] + full_l[-m] - a_l[m - 1], (m <= dl && W - m <= dr) ? 0u : 1u};
-                    const StrandScores ds = strand_scores(w, min_val);
-                    key_d = max(key_d, edit_key(ds.plus, -m, true));
-                    if (!forward_only) key_d = max(key_d, edit_key(ds.minus, -m, false));
-                    sum_d += walk_value(wtab, w, min_val, forward_only);
+                    del.add(strand_scores(w, min_val), -m, forward_only, walk_value(wtab, w, min_val, forward_only));
                 }
-                keys[cell] = make_uint2(key_c, key_d);
-                sums[cell] = make_ulonglong2(sum_c, sum_d);
+                store_cell(keys, sums, cell, cover, del);
             }
         }
     }
@@ -203,78 +173,31 @@ GFM_API int gfm_sequence_deletion_scan(const gfm_motif_t *motifs, int32_t n_moti
                                        int32_t n_lengths, const int32_t *lengths, uint32_t flags, uint32_t *const *d_keys,
                                        uint64_t *const *d_sums, int32_t *d_status, void *stream)
 {
+    const std::string entry = "gfm_sequence_deletion_scan";
     if (n_motifs < 1 || n_seqs < 0 || n_lengths < 1) return gfail(GFM_ERR_INVALID, "bad argument");
     if (flags & ~(uint32_t)GFM_GRAPH_FORWARD_ONLY) return gfail(GFM_ERR_INVALID, "unknown flag");
-    // ---- the lengths: strictly ascending within 1 .. GFM_DELSCAN_MAX_LENGTH, as a mask
-    if (!lengths) return gfail(GFM_ERR_INVALID, "gfm_sequence_deletion_scan: NULL argument");
+    // ---- the lengths, checked with no sequence too
     unsigned long long mask = 0ull;
-    for (int i = 0; i < n_lengths; ++i) {
-        if (lengths[i] < 1 || lengths[i] > kDsMaxLen)
-            return gfail(GFM_ERR_INVALID, "gfm_sequence_deletion_scan: length " + std::to_string(lengths[i]) + " is outside 1 .. " +
-                                          std::to_string(kDsMaxLen));
-        if (i > 0 && lengths[i] <= lengths[i - 1])
-            return gfail(GFM_ERR_INVALID, "gfm_sequence_deletion_scan: the lengths do not strictly ascend at " + std::to_string(i));
-        mask |= 1ull << (lengths[i] - 1);
-    }
+    if (const int rc = length_mask(entry, n_lengths, lengths, kDsMaxLen, mask)) return rc;
     const int lmax = lengths[n_lengths - 1];
     if (n_seqs == 0) return GFM_OK;
-    if (!seq_offsets) return gfail(GFM_ERR_INVALID, "gfm_sequence_deletion_scan: NULL argument");
-    // ---- the sequences and their tiles
-    if (seq_offsets[0] < 0) return gfail(GFM_ERR_INVALID, "gfm_sequence_deletion_scan: seq_offsets descends below 0");
-    std::vector<MsTile> tiles;
-    for (int v = 0; v < n_seqs; ++v) {
-        const long long a = seq_offsets[v], b = seq_offsets[v + 1];
-        if (b < a) return gfail(GFM_ERR_INVALID, "gfm_sequence_deletion_scan: seq_offsets descends at sequence " + std::to_string(v));
-        if (b - a > 0x7fffffffll)
-            return gfail(GFM_ERR_INVALID, "gfm_sequence_deletion_scan: sequence " + std::to_string(v) + " holds 2^31 bases or more");
-        for (long long s = 0; s < b - a; s += kDsTile) tiles.push_back(MsTile{a, (int)(b - a), (int)s});
-    }
-    const long long n_bases = seq_offsets[n_seqs];
+    std::vector<SeqTile> tiles;
+    if (const int rc = seq_tiles(entry, kDsTile, n_seqs, seq_offsets, tiles)) return rc;
     if (tiles.empty()) return GFM_OK;
-    if (!motifs || !d_weights || !d_keys || !d_sums || !d_status || !d_bases)
-        return gfail(GFM_ERR_INVALID, "gfm_sequence_deletion_scan: NULL argument");
-    for (int m = 0; m < n_motifs; ++m)
-        if (!motifs[m] || !d_weights[m] || !d_keys[m] || !d_sums[m]) return gfail(GFM_ERR_INVALID, "NULL motif / device buffer");
-    for (int m = 0; m < n_motifs; ++m)                            // (a cell is stored as one 8-byte and one 16-byte word)
-        if ((reinterpret_cast<uintptr_t>(d_keys[m]) & 7u) || (reinterpret_cast<uintptr_t>(d_sums[m]) & 15u))
-            return gfail(GFM_ERR_INVALID, "gfm_sequence_deletion_scan: d_keys[m] is 8-byte and d_sums[m] 16-byte aligned");
+    if (const int rc = check_scan_buffers(entry, motifs, n_motifs, d_weights, d_keys, d_sums, d_status, d_bases)) return rc;
+    if (const int rc = check_cell_alignment(entry, n_motifs, d_keys, d_sums)) return rc;
     MotifSet ms;
     if (const int rc = view_motif_set(motifs, n_motifs, ScoreBits::PackedTable, ms)) return rc;
     const int W = ms.W;
-    const unsigned side = delscan_side_windows(W, lmax);
-    if (!delscan_sum_fits(max_weight, W, lmax))
-        return gfail(GFM_ERR_INVALID, "gfm_sequence_deletion_scan: a side holds up to " + std::to_string(side) +
-                                      " windows (W = " + std::to_string(W) + ", longest length " + std::to_string(lmax) +
-                                      "): with weights up to " + std::to_string((unsigned long long)max_weight) +
-                                      " a sum may pass 2^64 - 1");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    GX_TRY(hipMemsetAsync(d_status, 0, sizeof(int32_t), st));
-    // ---- the scratch: the tile table (the host copy outlives the upload: the entry waits for the stream)
-    const size_t tile_bytes = align256(sizeof(MsTile) * tiles.size());
-    MsTile *d_tiles = nullptr;
-    GX_TRY(hipMallocAsync(reinterpret_cast<void **>(&d_tiles), tile_bytes, st));
-    hipError_t e = hipMemcpyAsync(d_tiles, tiles.data(), sizeof(MsTile) * tiles.size(), hipMemcpyHostToDevice, st);
-    const unsigned blocks = (unsigned)std::min<size_t>(tiles.size(), (size_t)kMsMaxBlocks);
+    if (const int rc = check_sum_capacity(entry, max_weight, delscan_side_windows(W, lmax),
+                                          " (W = " + std::to_string(W) + ", longest length " + std::to_string(lmax) + ")"))
+        return rc;
+    const long long n_bases = seq_offsets[n_seqs];
     const int fwd = (flags & GFM_GRAPH_FORWARD_ONLY) ? 1 : 0;
-    for (int m0 = 0; e == hipSuccess && m0 < n_motifs; m0 += kSeqMotifs) {
-        const int mm = std::min(kSeqMotifs, n_motifs - m0);
-        DsResults res = {};
-        for (int k = 0; k < mm; ++k) {
-            res.keys[k] = reinterpret_cast<uint2 *>(d_keys[m0 + k]);
-            res.sums[k] = reinterpret_cast<ulonglong2 *>(d_sums[m0 + k]);
-        }
-        hipLaunchKernelGGL(deletion_scan_kernel, dim3(blocks, (unsigned)mm), dim3(kDsThreads), delscan_lds_bytes(W, lmax), st,
-                           d_tiles, (long long)tiles.size(), d_bases, n_bases, seq_motifs(ms, d_weights, m0, mm), res, W, mask, fwd,
-                           d_status);
-        e = hipGetLastError();
-    }
-    int32_t verdict = 0;
-    if (e == hipSuccess) e = hipMemcpyAsync(&verdict, d_status, sizeof verdict, hipMemcpyDeviceToHost, st);
-    const hipError_t ef = hipFreeAsync(d_tiles, st);
-    const hipError_t es = hipStreamSynchronize(st);              // (also on failure: the tile table's host copy is still read)
-    if (e == hipSuccess) e = ef;
-    if (e == hipSuccess) e = es;
-    if (e != hipSuccess) return gfail(GFM_ERR_HIP, std::string("gfm_sequence_deletion_scan: ") + hipGetErrorString(e));
-    if (verdict & kMsBadTile) return gfail(GFM_ERR_INVALID, "gfm_sequence_deletion_scan: a tile lies outside its sequence");
-    return GFM_OK;
+    return run_seq_tiles(entry, tiles, n_motifs, d_status, stream,
+                         [&](int m0, int mm, unsigned blocks, const SeqTile *d_tiles, long long n_tiles, hipStream_t st) {
+        hipLaunchKernelGGL(deletion_scan_kernel, dim3(blocks, (unsigned)mm), dim3(kDsThreads), delscan_lds_bytes(W, lmax), st, d_tiles,
+                           n_tiles, d_bases, n_bases, seq_motifs(ms, d_weights, m0, mm),
+                           seq_results<CellResults>(d_keys, d_sums, m0, mm), W, mask, fwd, d_status);
+    });
 }

@@ -1,7 +1,8 @@
 // gfm_graph_indel_scan.hpp -- indel scan: the deletion of every base of a spelled sequence and the insertion of every base
 // behind it, every window the edit touches scored before and after on both strands (included at the end of graph_extract.hip
-// behind gfm_graph_mutation_scan.hpp, whose MsTile, MsResults, kMsBadTile and kMsMaxBlocks it shares; it uses base_code,
-// view_motif_set, SeqMotifs, GX_TRY, gfail, align256 and gfm_graph_table_score.hpp's strand_scores, walk_value and edit_key).
+// behind gfm_graph_mutation_scan.hpp; gfm_sequence_tiles.hpp gives it SeqTile, ColumnResults, SideBest, the tile check, the
+// table staging and the host protocol; it uses base_code, view_motif_set, SeqMotifs, gfail and gfm_graph_table_score.hpp's
+// strand_scores and walk_value).
 // Where query_edits_kernel scores the up to W windows of ONE edited sequence with W lookups each, this kernel scores every
 // window start of a sequence ONCE, keeps the running prefixes of that one pass, and makes every window of all 5 n edited
 // sequences from two of the pieces: an edited window is the head of one scored window and the tail of its neighbour.
@@ -72,8 +73,8 @@ __device__ __forceinline__ unsigned long long bits_from(unsigned long long lo, u
 }
 
 __global__ void __launch_bounds__(kIsThreads)
-indel_scan_kernel(const MsTile *__restrict__ tiles, long long n_tiles, const uint8_t *__restrict__ bases, long long n_bases,
-                  SeqMotifs mt, MsResults res, int W, int forward_only, int *__restrict__ status)
+indel_scan_kernel(const SeqTile *__restrict__ tiles, long long n_tiles, const uint8_t *__restrict__ bases, long long n_bases,
+                  SeqMotifs mt, ColumnResults res, int W, int forward_only, int *__restrict__ status)
 {
     extern __shared__ unsigned a_s[];                             // A(lo + row, m) at [row * stride + m - 1], m = 1 .. W
     __shared__ unsigned ftab_s[GFM_MAX_WIDTH * 8];
@@ -81,19 +82,15 @@ indel_scan_kernel(const MsTile *__restrict__ tiles, long long n_tiles, const uin
     __shared__ unsigned wsum_s[kIsWindows];
     __shared__ unsigned char code_s[kIsCodes];
     const int mi = blockIdx.y, tid = threadIdx.x;
-    for (int i = tid; i < W * 8; i += kIsThreads) ftab_s[i] = mt.ftab[mi][i];
+    stage_table(ftab_s, mt.ftab[mi], W, kIsThreads);
     const unsigned long long *__restrict__ wtab = mt.wtab[mi];
     unsigned *__restrict__ keys = res.keys[mi];
     unsigned long long *__restrict__ sums = res.sums[mi];
     const int min_val = mt.min_val[mi];
     const int stride = indel_stride(W);
     for (long long t = blockIdx.x; t < n_tiles; t += gridDim.x) {
-        const MsTile tile = tiles[t];
-        // ---- the tile, checked: everything read and written below lies inside its sequence (uniform: no thread stays behind)
-        if (tile.begin < 0 || tile.len <= 0 || tile.begin > n_bases - tile.len || tile.start < 0 || tile.start >= tile.len) {
-            if (tid == 0) atomicOr(status, kMsBadTile);
-            continue;
-        }
+        const SeqTile tile = tiles[t];
+        if (seq_tile_bad(tile, n_bases, status)) continue;
         const uint8_t *__restrict__ x = bases + tile.begin;
         const int len = tile.len, lo = tile.start, nt = min(kIsTile, len - lo);
         __syncthreads();                                          // (the table is staged; the last tile's rows are read)
@@ -135,8 +132,7 @@ indel_scan_kernel(const MsTile *__restrict__ tiles, long long n_tiles, const uin
             const int dr = behind ? __builtin_ctzll(behind) : 64;
             const int dl0 = xbad ? 0 : dl + 1;
             const unsigned *a_o = a_s + tid * stride, *a_o1 = a_o + stride;         // A(o, m) = a_o[m - 1], A(o + 1, m) = a_o1[m - 1]
-            unsigned key_c = 0u, key_d = 0u, key_j = 0u, key_b[4] = {0u, 0u, 0u, 0u};
-            unsigned long long sum_c = 0ull, sum_d = 0ull, sum_j = 0ull, sum_b[4] = {0ull, 0ull, 0ull, 0ull};
+            SideBest cover, del, junction, ins[4];
             unsigned a1 = 0u, full_next = 0u;                     // A(o + 1, m) and Full[o - m + 1], from the turn before
             for (int m = 0; m < W; ++m) {
                 const int k = tid + W - 1 - m;                    // the window start o - m
@@ -146,31 +142,19 @@ indel_scan_kernel(const MsTile *__restrict__ tiles, long long n_tiles, const uin
                     const WindowSum w{full, (m <= dl && !xbad && W - 1 - m <= dr) ? 0u : 1u};
                     const StrandScores rs = strand_scores(w, min_val);
                     const unsigned long long v = wref_s[k];
-                    key_c = max(key_c, edit_key(rs.plus, -m, true));
-                    if (!forward_only) key_c = max(key_c, edit_key(rs.minus, -m, false));
-                    sum_c += v;
-                    if (m <= W - 2) {
-                        key_j = max(key_j, edit_key(rs.plus, -m - 1, true));
-                        if (!forward_only) key_j = max(key_j, edit_key(rs.minus, -m - 1, false));
-                        sum_j += v;
-                    }
+                    cover.add(rs, -m, forward_only, v);
+                    if (m <= W - 2) junction.add(rs, -m - 1, forward_only, v);
                 }
                 if (m >= 1 && m <= o && W - m <= r) {             // DEL: x[o - m .. o - 1] and x[o + 1 .. o + W - m]
                     const WindowSum w{a_o[m - 1] + full_next - a1, (m <= dl && W - m <= dr) ? 0u : 1u};
-                    const StrandScores ds = strand_scores(w, min_val);
-                    key_d = max(key_d, edit_key(ds.plus, -m, true));
-                    if (!forward_only) key_d = max(key_d, edit_key(ds.minus, -m, false));
-                    sum_d += walk_value(wtab, w, min_val, forward_only);
+                    del.add(strand_scores(w, min_val), -m, forward_only, walk_value(wtab, w, min_val, forward_only));
                 }
                 if (m <= o + 1 && tail_x) {                       // INS_*: x[o + 1 - m .. o], b, x[o + 1 .. o + W - 1 - m]
                     const unsigned rest = a1 + full - a1n, invalid = (m <= dl0 && W - 1 - m <= dr) ? 0u : 1u;
 #pragma unroll
                     for (unsigned b = 0; b < 4; ++b) {
                         const WindowSum wb{rest + ftab_s[m * 8 + b], invalid};
-                        const StrandScores is = strand_scores(wb, min_val);
-                        key_b[b] = max(key_b[b], edit_key(is.plus, -m, true));
-                        if (!forward_only) key_b[b] = max(key_b[b], edit_key(is.minus, -m, false));
-                        sum_b[b] += walk_value(wtab, wb, min_val, forward_only);
+                        ins[b].add(strand_scores(wb, min_val), -m, forward_only, walk_value(wtab, wb, min_val, forward_only));
                     }
                 }
                 a1 = a1n;
@@ -179,8 +163,10 @@ indel_scan_kernel(const MsTile *__restrict__ tiles, long long n_tiles, const uin
             // the columns COVER, DEL, JUNCTION, INS_A, INS_C, INS_G, INS_T; the codes are A 0, C 1, T 2, G 3
             unsigned *kq = keys + (tile.begin + o) * 7;
             unsigned long long *sq = sums + (tile.begin + o) * 7;
-            kq[0] = key_c; kq[1] = key_d; kq[2] = key_j; kq[3] = key_b[0]; kq[4] = key_b[1]; kq[5] = key_b[3]; kq[6] = key_b[2];
-            sq[0] = sum_c; sq[1] = sum_d; sq[2] = sum_j; sq[3] = sum_b[0]; sq[4] = sum_b[1]; sq[5] = sum_b[3]; sq[6] = sum_b[2];
+            kq[0] = cover.key; kq[1] = del.key; kq[2] = junction.key;
+            kq[3] = ins[0].key; kq[4] = ins[1].key; kq[5] = ins[3].key; kq[6] = ins[2].key;
+            sq[0] = cover.sum; sq[1] = del.sum; sq[2] = junction.sum;
+            sq[3] = ins[0].sum; sq[4] = ins[1].sum; sq[5] = ins[3].sum; sq[6] = ins[2].sum;
         }
     }
 }
@@ -192,61 +178,25 @@ GFM_API int gfm_sequence_indel_scan(const gfm_motif_t *motifs, int32_t n_motifs,
                                     uint32_t flags, uint32_t *const *d_keys, uint64_t *const *d_sums, int32_t *d_status,
                                     void *stream)
 {
+    const std::string entry = "gfm_sequence_indel_scan";
     if (n_motifs < 1 || n_seqs < 0) return gfail(GFM_ERR_INVALID, "bad argument");
     if (flags & ~(uint32_t)GFM_GRAPH_FORWARD_ONLY) return gfail(GFM_ERR_INVALID, "unknown flag");
     if (n_seqs == 0) return GFM_OK;
-    if (!seq_offsets) return gfail(GFM_ERR_INVALID, "gfm_sequence_indel_scan: NULL argument");
-    // ---- the sequences and their tiles
-    if (seq_offsets[0] < 0) return gfail(GFM_ERR_INVALID, "gfm_sequence_indel_scan: seq_offsets descends below 0");
-    std::vector<MsTile> tiles;
-    for (int v = 0; v < n_seqs; ++v) {
-        const long long a = seq_offsets[v], b = seq_offsets[v + 1];
-        if (b < a) return gfail(GFM_ERR_INVALID, "gfm_sequence_indel_scan: seq_offsets descends at sequence " + std::to_string(v));
-        if (b - a > 0x7fffffffll)
-            return gfail(GFM_ERR_INVALID, "gfm_sequence_indel_scan: sequence " + std::to_string(v) + " holds 2^31 bases or more");
-        for (long long s = 0; s < b - a; s += kIsTile) tiles.push_back(MsTile{a, (int)(b - a), (int)s});
-    }
-    const long long n_bases = seq_offsets[n_seqs];
+    std::vector<SeqTile> tiles;
+    if (const int rc = seq_tiles(entry, kIsTile, n_seqs, seq_offsets, tiles)) return rc;
     if (tiles.empty()) return GFM_OK;
-    if (!motifs || !d_weights || !d_keys || !d_sums || !d_status || !d_bases)
-        return gfail(GFM_ERR_INVALID, "gfm_sequence_indel_scan: NULL argument");
-    for (int m = 0; m < n_motifs; ++m)
-        if (!motifs[m] || !d_weights[m] || !d_keys[m] || !d_sums[m]) return gfail(GFM_ERR_INVALID, "NULL motif / device buffer");
+    if (const int rc = check_scan_buffers(entry, motifs, n_motifs, d_weights, d_keys, d_sums, d_status, d_bases)) return rc;
     MotifSet ms;
     if (const int rc = view_motif_set(motifs, n_motifs, ScoreBits::PackedTable, ms)) return rc;
     const int W = ms.W;
     // the capacity of a sum: a side has at most W windows, each once per strand
-    if ((unsigned __int128)max_weight * 2u * (unsigned)W > (unsigned __int128)UINT64_MAX)
-        return gfail(GFM_ERR_INVALID, "gfm_sequence_indel_scan: a side holds up to " + std::to_string(2 * W) +
-                                      " windows: with weights up to " + std::to_string((unsigned long long)max_weight) +
-                                      " a sum may pass 2^64 - 1");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    GX_TRY(hipMemsetAsync(d_status, 0, sizeof(int32_t), st));
-    // ---- the scratch: the tile table (the host copy outlives the upload: the entry waits for the stream)
-    const size_t tile_bytes = align256(sizeof(MsTile) * tiles.size());
-    MsTile *d_tiles = nullptr;
-    GX_TRY(hipMallocAsync(reinterpret_cast<void **>(&d_tiles), tile_bytes, st));
-    hipError_t e = hipMemcpyAsync(d_tiles, tiles.data(), sizeof(MsTile) * tiles.size(), hipMemcpyHostToDevice, st);
-    const unsigned blocks = (unsigned)std::min<size_t>(tiles.size(), (size_t)kMsMaxBlocks);
+    if (const int rc = check_sum_capacity(entry, max_weight, 2u * (unsigned)W, "")) return rc;
+    const long long n_bases = seq_offsets[n_seqs];
     const int fwd = (flags & GFM_GRAPH_FORWARD_ONLY) ? 1 : 0;
-    for (int m0 = 0; e == hipSuccess && m0 < n_motifs; m0 += kSeqMotifs) {
-        const int mm = std::min(kSeqMotifs, n_motifs - m0);
-        MsResults res = {};
-        for (int k = 0; k < mm; ++k) {
-            res.keys[k] = d_keys[m0 + k];
-            res.sums[k] = reinterpret_cast<unsigned long long *>(d_sums[m0 + k]);
-        }
-        hipLaunchKernelGGL(indel_scan_kernel, dim3(blocks, (unsigned)mm), dim3(kIsThreads), indel_lds_bytes(W), st, d_tiles,
-                           (long long)tiles.size(), d_bases, n_bases, seq_motifs(ms, d_weights, m0, mm), res, W, fwd, d_status);
-        e = hipGetLastError();
-    }
-    int32_t verdict = 0;
-    if (e == hipSuccess) e = hipMemcpyAsync(&verdict, d_status, sizeof verdict, hipMemcpyDeviceToHost, st);
-    const hipError_t ef = hipFreeAsync(d_tiles, st);
-    const hipError_t es = hipStreamSynchronize(st);              // (also on failure: the tile table's host copy is still read)
-    if (e == hipSuccess) e = ef;
-    if (e == hipSuccess) e = es;
-    if (e != hipSuccess) return gfail(GFM_ERR_HIP, std::string("gfm_sequence_indel_scan: ") + hipGetErrorString(e));
-    if (verdict & kMsBadTile) return gfail(GFM_ERR_INVALID, "gfm_sequence_indel_scan: a tile lies outside its sequence");
-    return GFM_OK;
+    return run_seq_tiles(entry, tiles, n_motifs, d_status, stream,
+                         [&](int m0, int mm, unsigned blocks, const SeqTile *d_tiles, long long n_tiles, hipStream_t st) {
+        hipLaunchKernelGGL(indel_scan_kernel, dim3(blocks, (unsigned)mm), dim3(kIsThreads), indel_lds_bytes(W), st, d_tiles, n_tiles,
+                           d_bases, n_bases, seq_motifs(ms, d_weights, m0, mm), seq_results<ColumnResults>(d_keys, d_sums, m0, mm), W,
+                           fwd, d_status);
+    });
 }

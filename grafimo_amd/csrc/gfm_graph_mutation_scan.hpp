@@ -1,7 +1,11 @@
 // gfm_graph_mutation_scan.hpp -- mutation scan: every single-base change at every offset of a spelled sequence, every window
 // the change touches scored before and after on both strands (included at the end of graph_extract.hip behind
-// gfm_graph_query_variants.hpp; it uses base_code, view_motif_set, SeqMotifs, GX_TRY, gfail, align256 and
-// gfm_graph_table_score.hpp's window_sum, strand_scores, walk_value and edit_key).  Where query_edits_kernel
+// gfm_sequence_tiles.hpp, whose SeqTile, ColumnResults and host side -- the offset walk, the buffer checks, the capacity rule
+// and the protocol around the launches -- it uses, with base_code, view_motif_set, SeqMotifs, gfail and
+// gfm_graph_table_score.hpp's window_sum, strand_scores, walk_value and edit_key.  The KERNEL shares none of that header's
+// device functions: with SideBest for its five columns it took two more VGPRs and measured 1 to 2 % slower, so its device
+// code is instruction for instruction what it was, profiles/sequence_scan_refactor.txt).
+// Where query_edits_kernel
 // scores the 2 W windows of ONE edit with W lookups each, this kernel scores every window of a sequence ONCE and derives the
 // windows of all 4 n changes from the stored sums: an ALT window differs from its REF window in one table entry.
 //
@@ -37,22 +41,10 @@ constexpr int kMsTile = GFM_MUTSCAN_TILE, kMsThreads = kMsTile;
 constexpr int kMsHalo = GFM_MAX_WIDTH - 1;
 constexpr int kMsCodes = (kMsTile + 2 * kMsHalo + 15) & ~15;                        // 192
 constexpr int kMsWindows = (kMsTile + kMsHalo + 15) & ~15;                          // 128
-constexpr int kMsMaxBlocks = 1 << 16;
-constexpr int kMsBadTile = 1;
-
-struct MsTile {
-    long long begin;              // the sequence's first base in d_bases (and its first row in the results)
-    int len, start;               // its length; the tile's first offset
-};
-
-struct MsResults {
-    unsigned *keys[kSeqMotifs];
-    unsigned long long *sums[kSeqMotifs];
-};
 
 __global__ void __launch_bounds__(kMsThreads)
-mutation_scan_kernel(const MsTile *__restrict__ tiles, long long n_tiles, const uint8_t *__restrict__ bases, long long n_bases,
-                     SeqMotifs mt, MsResults res, int W, int forward_only, int *__restrict__ status)
+mutation_scan_kernel(const SeqTile *__restrict__ tiles, long long n_tiles, const uint8_t *__restrict__ bases, long long n_bases,
+                     SeqMotifs mt, ColumnResults res, int W, int forward_only, int *__restrict__ status)
 {
     __shared__ unsigned ftab_s[GFM_MAX_WIDTH * 8];
     __shared__ unsigned long long wref_s[kMsWindows];
@@ -66,10 +58,10 @@ mutation_scan_kernel(const MsTile *__restrict__ tiles, long long n_tiles, const 
     const int min_val = mt.min_val[m];
     const int halo = W - 1;
     for (long long t = blockIdx.x; t < n_tiles; t += gridDim.x) {
-        const MsTile tile = tiles[t];
+        const SeqTile tile = tiles[t];
         // ---- the tile, checked: everything read and written below lies inside its sequence (uniform: no thread stays behind)
         if (tile.begin < 0 || tile.len <= 0 || tile.begin > n_bases - tile.len || tile.start < 0 || tile.start >= tile.len) {
-            if (tid == 0) atomicOr(status, kMsBadTile);
+            if (tid == 0) atomicOr(status, kSeqBadTile);
             continue;
         }
         const uint8_t *__restrict__ x = bases + tile.begin;
@@ -135,61 +127,25 @@ GFM_API int gfm_sequence_mutation_scan(const gfm_motif_t *motifs, int32_t n_moti
                                        uint32_t flags, uint32_t *const *d_keys, uint64_t *const *d_sums, int32_t *d_status,
                                        void *stream)
 {
+    const std::string entry = "gfm_sequence_mutation_scan";
     if (n_motifs < 1 || n_seqs < 0) return gfail(GFM_ERR_INVALID, "bad argument");
     if (flags & ~(uint32_t)GFM_GRAPH_FORWARD_ONLY) return gfail(GFM_ERR_INVALID, "unknown flag");
     if (n_seqs == 0) return GFM_OK;
-    if (!seq_offsets) return gfail(GFM_ERR_INVALID, "gfm_sequence_mutation_scan: NULL argument");
-    // ---- the sequences and their tiles
-    if (seq_offsets[0] < 0) return gfail(GFM_ERR_INVALID, "gfm_sequence_mutation_scan: seq_offsets descends below 0");
-    std::vector<MsTile> tiles;
-    for (int v = 0; v < n_seqs; ++v) {
-        const long long a = seq_offsets[v], b = seq_offsets[v + 1];
-        if (b < a) return gfail(GFM_ERR_INVALID, "gfm_sequence_mutation_scan: seq_offsets descends at sequence " + std::to_string(v));
-        if (b - a > 0x7fffffffll)
-            return gfail(GFM_ERR_INVALID, "gfm_sequence_mutation_scan: sequence " + std::to_string(v) + " holds 2^31 bases or more");
-        for (long long s = 0; s < b - a; s += kMsTile) tiles.push_back(MsTile{a, (int)(b - a), (int)s});
-    }
-    const long long n_bases = seq_offsets[n_seqs];
+    std::vector<SeqTile> tiles;
+    if (const int rc = seq_tiles(entry, kMsTile, n_seqs, seq_offsets, tiles)) return rc;
     if (tiles.empty()) return GFM_OK;
-    if (!motifs || !d_weights || !d_keys || !d_sums || !d_status || !d_bases)
-        return gfail(GFM_ERR_INVALID, "gfm_sequence_mutation_scan: NULL argument");
-    for (int m = 0; m < n_motifs; ++m)
-        if (!motifs[m] || !d_weights[m] || !d_keys[m] || !d_sums[m]) return gfail(GFM_ERR_INVALID, "NULL motif / device buffer");
+    if (const int rc = check_scan_buffers(entry, motifs, n_motifs, d_weights, d_keys, d_sums, d_status, d_bases)) return rc;
     MotifSet ms;
     if (const int rc = view_motif_set(motifs, n_motifs, ScoreBits::PackedTable, ms)) return rc;
     const int W = ms.W;
     // the capacity of a sum: a side has at most W windows, each once per strand
-    if ((unsigned __int128)max_weight * 2u * (unsigned)W > (unsigned __int128)UINT64_MAX)
-        return gfail(GFM_ERR_INVALID, "gfm_sequence_mutation_scan: a side holds up to " + std::to_string(2 * W) +
-                                      " windows: with weights up to " + std::to_string((unsigned long long)max_weight) +
-                                      " a sum may pass 2^64 - 1");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    GX_TRY(hipMemsetAsync(d_status, 0, sizeof(int32_t), st));
-    // ---- the scratch: the tile table (the host copy outlives the upload: the entry waits for the stream)
-    const size_t tile_bytes = align256(sizeof(MsTile) * tiles.size());
-    MsTile *d_tiles = nullptr;
-    GX_TRY(hipMallocAsync(reinterpret_cast<void **>(&d_tiles), tile_bytes, st));
-    hipError_t e = hipMemcpyAsync(d_tiles, tiles.data(), sizeof(MsTile) * tiles.size(), hipMemcpyHostToDevice, st);
-    const unsigned blocks = (unsigned)std::min<size_t>(tiles.size(), (size_t)kMsMaxBlocks);
+    if (const int rc = check_sum_capacity(entry, max_weight, 2u * (unsigned)W, "")) return rc;
+    const long long n_bases = seq_offsets[n_seqs];
     const int fwd = (flags & GFM_GRAPH_FORWARD_ONLY) ? 1 : 0;
-    for (int m0 = 0; e == hipSuccess && m0 < n_motifs; m0 += kSeqMotifs) {
-        const int mm = std::min(kSeqMotifs, n_motifs - m0);
-        MsResults res = {};
-        for (int k = 0; k < mm; ++k) {
-            res.keys[k] = d_keys[m0 + k];
-            res.sums[k] = reinterpret_cast<unsigned long long *>(d_sums[m0 + k]);
-        }
-        hipLaunchKernelGGL(mutation_scan_kernel, dim3(blocks, (unsigned)mm), dim3(kMsThreads), 0, st, d_tiles,
-                           (long long)tiles.size(), d_bases, n_bases, seq_motifs(ms, d_weights, m0, mm), res, W, fwd, d_status);
-        e = hipGetLastError();
-    }
-    int32_t verdict = 0;
-    if (e == hipSuccess) e = hipMemcpyAsync(&verdict, d_status, sizeof verdict, hipMemcpyDeviceToHost, st);
-    const hipError_t ef = hipFreeAsync(d_tiles, st);
-    const hipError_t es = hipStreamSynchronize(st);              // (also on failure: the tile table's host copy is still read)
-    if (e == hipSuccess) e = ef;
-    if (e == hipSuccess) e = es;
-    if (e != hipSuccess) return gfail(GFM_ERR_HIP, std::string("gfm_sequence_mutation_scan: ") + hipGetErrorString(e));
-    if (verdict & kMsBadTile) return gfail(GFM_ERR_INVALID, "gfm_sequence_mutation_scan: a tile lies outside its sequence");
-    return GFM_OK;
+    return run_seq_tiles(entry, tiles, n_motifs, d_status, stream,
+                         [&](int m0, int mm, unsigned blocks, const SeqTile *d_tiles, long long n_tiles, hipStream_t st) {
+        hipLaunchKernelGGL(mutation_scan_kernel, dim3(blocks, (unsigned)mm), dim3(kMsThreads), 0, st, d_tiles, n_tiles, d_bases,
+                           n_bases, seq_motifs(ms, d_weights, m0, mm), seq_results<ColumnResults>(d_keys, d_sums, m0, mm), W, fwd,
+                           d_status);
+    });
 }

@@ -1,8 +1,8 @@
 // gfm_graph_site_distance.hpp -- site distance: for every window of a spelled sequence, the least number of substitutions
 // that lifts it over a score cutoff (the near side) and the least number that drops a site under it (the fragile side), with
 // the columns picked (included at the end of graph_extract.hip behind gfm_graph_substitution_scan.hpp; it uses base_code,
-// view_motif_set, SeqMotifs, GX_TRY, gfail, align256, gfm_graph_table_score.hpp's window_sum and the mutation scan's MsTile,
-// kMsMaxBlocks and kMsBadTile).  Where the scans before it enumerate their edits and score every one, this kernel selects: a
+// view_motif_set, SeqMotifs, gfail, gfm_graph_table_score.hpp's window_sum and gfm_sequence_tiles.hpp's SeqTile, offset walk
+// and host protocol; the kernel's device code is its own, as the mutation scan's is).  Where the scans before it enumerate their edits and score every one, this kernel selects: a
 // PWM is additive, so the best set of k columns to change is the k columns with the largest gains, and no set is enumerated.
 //
 // THE RULE (include/grafimo_hip.h states it for the library; tests/site_distance_bruteforce.py on the host).
@@ -99,7 +99,7 @@ __device__ __forceinline__ void sd_take(SdPick &p, unsigned best, int j, int c, 
 __device__ __forceinline__ unsigned sd_word(const SdPick &p) { return ((unsigned)p.score << 4) | (unsigned)p.d; }
 
 __global__ void __launch_bounds__(kSdThreads)
-site_distance_kernel(const MsTile *__restrict__ tiles, long long n_tiles, const uint8_t *__restrict__ bases, long long n_bases,
+site_distance_kernel(const SeqTile *__restrict__ tiles, long long n_tiles, const uint8_t *__restrict__ bases, long long n_bases,
                      SeqMotifs mt, SdResults res, int W, int E, int forward_only, int *__restrict__ status)
 {
     __shared__ unsigned ftab_s[GFM_MAX_WIDTH * 8];
@@ -122,10 +122,10 @@ site_distance_kernel(const MsTile *__restrict__ tiles, long long n_tiles, const 
     const int min_val = mt.min_val[m], c = res.cutoff[m];
     const int halo = W - 1;
     for (long long t = blockIdx.x; t < n_tiles; t += gridDim.x) {
-        const MsTile tile = tiles[t];
+        const SeqTile tile = tiles[t];
         // ---- the tile, checked: everything read and written below lies inside its sequence (uniform: no thread stays behind)
         if (tile.begin < 0 || tile.len <= 0 || tile.begin > n_bases - tile.len || tile.start < 0 || tile.start >= tile.len) {
-            if (tid == 0) atomicOr(status, kMsBadTile);
+            if (tid == 0) atomicOr(status, kSeqBadTile);
             continue;
         }
         const uint8_t *__restrict__ x = bases + tile.begin;
@@ -221,6 +221,7 @@ GFM_API int gfm_sequence_site_distance(const gfm_motif_t *motifs, int32_t n_moti
                                        const uint8_t *d_bases, const int32_t *cutoffs, int32_t max_edits, uint32_t flags,
                                        uint32_t *const *d_words, uint64_t *const *d_masks, int32_t *d_status, void *stream)
 {
+    const std::string entry = "gfm_sequence_site_distance";
     if (n_motifs < 1) return gfail(GFM_ERR_INVALID, "gfm_sequence_site_distance: n_motifs < 1");
     if (n_seqs < 0) return gfail(GFM_ERR_INVALID, "gfm_sequence_site_distance: n_seqs < 0");
     if (flags & ~(uint32_t)GFM_GRAPH_FORWARD_ONLY) return gfail(GFM_ERR_INVALID, "unknown flag");
@@ -234,16 +235,8 @@ GFM_API int gfm_sequence_site_distance(const gfm_motif_t *motifs, int32_t n_moti
             return gfail(GFM_ERR_INVALID, "gfm_sequence_site_distance: cutoff " + std::to_string(cutoffs[m]) + " of motif " +
                                           std::to_string(m) + " is outside 0 .. 1000 W + 1 for every width");
     // ---- the sequences and their tiles
-    if (n_seqs > 0 && !seq_offsets) return gfail(GFM_ERR_INVALID, "gfm_sequence_site_distance: NULL argument");
-    if (n_seqs > 0 && seq_offsets[0] < 0) return gfail(GFM_ERR_INVALID, "gfm_sequence_site_distance: seq_offsets descends below 0");
-    std::vector<MsTile> tiles;
-    for (int v = 0; v < n_seqs; ++v) {
-        const long long a = seq_offsets[v], b = seq_offsets[v + 1];
-        if (b < a) return gfail(GFM_ERR_INVALID, "gfm_sequence_site_distance: seq_offsets descends at sequence " + std::to_string(v));
-        if (b - a > 0x7fffffffll)
-            return gfail(GFM_ERR_INVALID, "gfm_sequence_site_distance: sequence " + std::to_string(v) + " holds 2^31 bases or more");
-        for (long long s = 0; s < b - a; s += kSdTile) tiles.push_back(MsTile{a, (int)(b - a), (int)s});
-    }
+    std::vector<SeqTile> tiles;
+    if (const int rc = seq_tiles(entry, kSdTile, n_seqs, seq_offsets, tiles)) return rc;
     // ---- the motifs: one width, and every cutoff within that width's scores -- looked at whenever the caller gives them
     if (!tiles.empty() && (!motifs || !d_words || !d_masks || !d_status || !d_bases))
         return gfail(GFM_ERR_INVALID, "gfm_sequence_site_distance: NULL argument");
@@ -265,17 +258,9 @@ GFM_API int gfm_sequence_site_distance(const gfm_motif_t *motifs, int32_t n_moti
                                           std::to_string(W) + ")");
     if (tiles.empty()) return GFM_OK;
     const long long n_bases = seq_offsets[n_seqs];
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    GX_TRY(hipMemsetAsync(d_status, 0, sizeof(int32_t), st));
-    // ---- the scratch: the tile table (the host copy outlives the upload: the entry waits for the stream)
-    const size_t tile_bytes = align256(sizeof(MsTile) * tiles.size());
-    MsTile *d_tiles = nullptr;
-    GX_TRY(hipMallocAsync(reinterpret_cast<void **>(&d_tiles), tile_bytes, st));
-    hipError_t e = hipMemcpyAsync(d_tiles, tiles.data(), sizeof(MsTile) * tiles.size(), hipMemcpyHostToDevice, st);
-    const unsigned blocks = (unsigned)std::min<size_t>(tiles.size(), (size_t)kMsMaxBlocks);
     const int fwd = (flags & GFM_GRAPH_FORWARD_ONLY) ? 1 : 0;
-    for (int m0 = 0; e == hipSuccess && m0 < n_motifs; m0 += kSeqMotifs) {
-        const int mm = std::min(kSeqMotifs, n_motifs - m0);
+    return run_seq_tiles(entry, tiles, n_motifs, d_status, stream,
+                         [&](int m0, int mm, unsigned blocks, const SeqTile *d_tiles, long long n_tiles, hipStream_t st) {
         SeqMotifs mt = {};
         SdResults res = {};
         for (int k = 0; k < mm; ++k) {
@@ -285,17 +270,7 @@ GFM_API int gfm_sequence_site_distance(const gfm_motif_t *motifs, int32_t n_moti
             res.masks[k] = reinterpret_cast<unsigned long long *>(d_masks[m0 + k]);
             res.cutoff[k] = cutoffs[m0 + k];
         }
-        hipLaunchKernelGGL(site_distance_kernel, dim3(blocks, (unsigned)mm), dim3(kSdThreads), 0, st, d_tiles,
-                           (long long)tiles.size(), d_bases, n_bases, mt, res, W, (int)max_edits, fwd, d_status);
-        e = hipGetLastError();
-    }
-    int32_t verdict = 0;
-    if (e == hipSuccess) e = hipMemcpyAsync(&verdict, d_status, sizeof verdict, hipMemcpyDeviceToHost, st);
-    const hipError_t ef = hipFreeAsync(d_tiles, st);
-    const hipError_t es = hipStreamSynchronize(st);              // (also on failure: the tile table's host copy is still read)
-    if (e == hipSuccess) e = ef;
-    if (e == hipSuccess) e = es;
-    if (e != hipSuccess) return gfail(GFM_ERR_HIP, std::string("gfm_sequence_site_distance: ") + hipGetErrorString(e));
-    if (verdict & kMsBadTile) return gfail(GFM_ERR_INVALID, "gfm_sequence_site_distance: a tile lies outside its sequence");
-    return GFM_OK;
+        hipLaunchKernelGGL(site_distance_kernel, dim3(blocks, (unsigned)mm), dim3(kSdThreads), 0, st, d_tiles, n_tiles, d_bases,
+                           n_bases, mt, res, W, (int)max_edits, fwd, d_status);
+    });
 }

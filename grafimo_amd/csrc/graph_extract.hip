@@ -2644,6 +2644,7 @@ inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 #include "gfm_graph_hapclasses.hpp"
 #include "gfm_graph_hapsequences.hpp"
 #include "gfm_graph_query_variants.hpp"
+#include "gfm_sequence_tiles.hpp"
 #include "gfm_graph_mutation_scan.hpp"
 #include "gfm_graph_indel_scan.hpp"
 #include "gfm_graph_deletion_scan.hpp"

@@ -31,21 +31,15 @@ The hot path is HIP (grafimo_amd/csrc/gfm_graph_deletion_scan.hpp, gfm_sequence_
 sequence is scored once for all lengths, and every junction window is put together from two stored pieces.  Everything from
 the kernel's arrays to the frames is numpy group-bys; there is no Python step per row or per base.
 """
-import contextlib
-import ctypes
-import sys
 from typing import List, Mapping, Optional, Sequence, Tuple
 
 import numpy as np
 import pandas as pd
 
 from . import _native as nv
-from .extract_regions import _stream_ptr, _torch
-from .graph_tables import (_haplotype_set, _matrix_rows, group_by_width, prepare_graphs, require_single_gpu, scaled_pvalues,
-                           scaled_scores, table_path, write_frame)
-from .mutation_scan import (_COMP, _UPPER, DEFAULT_MAX_BYTES, _checked_sequences, _leased_chunks, _with_references, effect_codes,
-                            group_summary, keep_rows)
-from .query_variants import EFFECTS, decode_keys
+from .query_variants import decode_keys
+from .sequence_scans import (_UPPER, DEFAULT_MAX_BYTES, ScanTable, _checked_sequences, _within, fixed_text, printed_windows,
+                             scan_chunked, scan_inputs, table_writers, tables_by_width)
 
 DETAIL_FILE = "grafimo_deletion_scan"
 SUMMARY_FILE = "grafimo_deletion_scan_summary"
@@ -70,47 +64,14 @@ def checked_lengths(lengths) -> np.ndarray:
 
 
 # ---------------------------------------------------------------------------------------------------------------- the kernel
-def _scan(dms, tables, seq_offsets: np.ndarray, bases: np.ndarray, lengths: np.ndarray, forward_only: bool):
-    """gfm_sequence_deletion_scan for leased motifs of one width -> (keys uint32 [M, n_lengths, N, 2], sums uint64 of that
-    shape).  The staging is this module's own: the entry takes the lengths and writes another shape than mutation_scan's."""
-    M, N, K = len(dms), int(seq_offsets[-1]), len(lengths)
-    if N == 0:
-        return np.zeros((M, K, 0, 2), dtype=np.uint32), np.zeros((M, K, 0, 2), dtype=np.uint64)
-    torch = _torch()
-    dev = torch.device("cuda", torch.cuda.current_device())
-    d_bases = torch.from_numpy(np.array(bases, dtype=np.uint8)).to(dev)              # (a copy: the caller's may be read-only)
-    d_tabs = [torch.from_numpy(np.ascontiguousarray(t, dtype=np.uint64).view(np.int64)).to(dev) for t in tables]
-    keys = torch.empty((M, K, N, 2), dtype=torch.int32, device=dev)
-    sums = torch.empty((M, K, N, 2), dtype=torch.int64, device=dev)
-    status = torch.zeros(1, dtype=torch.int32, device=dev)
-    vp = ctypes.c_void_p
-    nv.check(getattr(nv.lib(), ENTRY)(
-        (vp * M)(*[x.handle for x in dms]), M, (vp * M)(*[t.data_ptr() for t in d_tabs]), max(int(t.max()) for t in tables),
-        len(seq_offsets) - 1, seq_offsets.ctypes.data, d_bases.data_ptr(), K, lengths.ctypes.data,
-        nv.GFM_GRAPH_FORWARD_ONLY if forward_only else 0, (vp * M)(*[keys[m].data_ptr() for m in range(M)]),
-        (vp * M)(*[sums[m].data_ptr() for m in range(M)]), status.data_ptr(), _stream_ptr(None)))
-    return keys.cpu().numpy().view(np.uint32), sums.cpu().numpy().view(np.uint64)
-
-
-def _scan_chunked(motifs: Sequence, seq_offsets, bases, lengths, weights, temperature, forward_only, max_bytes):
-    """-> (per motif (keys, sums), per motif its log2 offset, per motif (scale, offset, ptable)): the motifs leased and scanned
-    in chunks whose result tensors (24 bytes a base, length and motif) stay under max_bytes"""
-    if weights is not None and len(weights) != len(motifs):
-        raise ValueError(f"{len(weights)} weight tables for {len(motifs)} motifs")
-    per_motif = BYTES_PER_CELL * len(lengths) * int(seq_offsets[-1])
-    if per_motif > int(max_bytes):
-        raise ValueError(f"{motifs[0].motif_id}: the keys and sums of one motif over {int(seq_offsets[-1])} bases and "
-                         f"{len(lengths)} lengths hold {per_motif} bytes, more than max_bytes = {int(max_bytes)}: scan fewer "
-                         f"sequences or lengths at a time, or raise max_bytes")
-    step = max(1, int(max_bytes) // max(per_motif, 1))
-    results, offsets, numbers = [], [], []
-    with contextlib.closing(_leased_chunks(motifs, weights, temperature, step)) as chunks:     # (a failure gives the handles back)
-        for _, dms, tables, offs, nums in chunks:
-            keys, sums = _scan(dms, tables, seq_offsets, bases, lengths, forward_only)
-            results += [(keys[m], sums[m]) for m in range(len(dms))]
-            offsets += offs
-            numbers += nums
-    return results, offsets, numbers
+def _scan_chunked(motifs: Sequence, seq_offsets, bases, lengths, weights, temperature, forward_only, max_bytes,
+                  entry: str = ENTRY, extra: Sequence = ()):
+    """-> (per motif (keys, sums) [n_lengths, N, 2], per motif its log2 offset, per motif (scale, offset, ptable)) of a block scan
+    (`entry`; `extra`: its arguments behind the lengths): the motifs leased and scanned in chunks whose result tensors (24 bytes a
+    base, length and motif) stay under max_bytes"""
+    K = len(lengths)
+    return scan_chunked(motifs, seq_offsets, bases, weights, temperature, forward_only, max_bytes, entry, (K, len(bases), len(COLUMNS)),
+                        (K, lengths.ctypes.data, *extra), f" and {K} lengths", " or lengths")
 
 
 def scan_sequences(motifs: Sequence, seq_offsets, bases, lengths, weights: Optional[Sequence[np.ndarray]] = None,
@@ -126,13 +87,6 @@ def scan_sequences(motifs: Sequence, seq_offsets, bases, lengths, weights: Optio
     lengths = checked_lengths(lengths)
     seq_offsets, bases = _checked_sequences(seq_offsets, bases)
     return _scan_chunked(motifs, seq_offsets, bases, lengths, weights, temperature, forward_only, max_bytes)[0]
-
-
-def _within(seq_offsets: np.ndarray, N: int):
-    """-> (the offset of every base in its sequence, the bases behind and including it) int64 [N]"""
-    n = np.diff(seq_offsets)
-    within = np.arange(N, dtype=np.int64) - np.repeat(seq_offsets[:-1], n)
-    return within, np.repeat(n, n) - within
 
 
 def leftmost_deletions(seq_offsets, bases, lengths) -> np.ndarray:
@@ -152,7 +106,7 @@ def leftmost_deletions(seq_offsets, bases, lengths) -> np.ndarray:
     return fits & ~repeat
 
 
-class DeletionScan:
+class DeletionScan(ScanTable):
     """The table of one motif over S sequences of N bases in all and K lengths (see the module's docstring).
     Per sequence [S]: seq_region, seq_version (-1: the region's reference sequence, which no haplotype spells), seq_count,
     seq_group_counts [S, G], seq_is_reference, seq_offsets int64 [S + 1] -- as IndelScan's.
@@ -163,38 +117,13 @@ class DeletionScan:
     def __init__(self, motif_id, motif_alt_id, width, scale, offset, ptable, log2_offset, threshold, region_names, group_names,
                  seq_region, seq_version, seq_count, seq_group_counts, seq_is_reference, seq_offsets, bases, coord, lengths, keys,
                  sums, delta=None, all_rows=False):
-        self.motif_id, self.motif_alt_id = motif_id, motif_alt_id
-        self.width, self.scale, self.offset = int(width), int(scale), float(offset)
-        self.ptable, self.log2_offset, self.threshold = np.asarray(ptable, dtype=np.float64), float(log2_offset), float(threshold)
-        self.region_names, self.group_names = np.asarray(region_names, dtype=object), list(group_names)
-        self.seq_region, self.seq_version = np.asarray(seq_region, dtype=np.int64), np.asarray(seq_version, dtype=np.int64)
-        self.seq_count = np.asarray(seq_count, dtype=np.int64)
-        self.seq_group_counts = np.asarray(seq_group_counts, dtype=np.int64).reshape(len(self.seq_count), len(self.group_names))
-        self.seq_is_reference = np.asarray(seq_is_reference, dtype=bool)
-        self.seq_offsets = np.asarray(seq_offsets, dtype=np.int64)
-        self.bases, self.coord = np.asarray(bases, dtype=np.uint8), np.asarray(coord, dtype=np.int32)
         self.lengths = checked_lengths(lengths)
-        self.keys, self.sums = np.asarray(keys, dtype=np.uint32), np.asarray(sums, dtype=np.uint64)
-        N, K = len(self.bases), len(self.lengths)
-        if self.keys.shape != (K, N, 2) or self.sums.shape != (K, N, 2) or len(self.coord) != N or int(self.seq_offsets[-1]) != N:
-            raise ValueError("the arrays do not fit the sequences and lengths")
-        self.delta = None if delta is None else float(delta)
-        self.all_rows = bool(all_rows)
+        super().__init__(motif_id, motif_alt_id, width, scale, offset, ptable, log2_offset, threshold, region_names, group_names,
+                         seq_region, seq_version, seq_count, seq_group_counts, seq_is_reference, seq_offsets, bases, coord, keys, sums,
+                         delta, all_rows)
 
-    def __len__(self) -> int:
-        return int(self._kept_cells()[0].size)
-
-    @property
-    def base_sequence(self) -> np.ndarray:
-        """int64 [N]: the sequence of every base"""
-        return np.repeat(np.arange(len(self.seq_count), dtype=np.int64), np.diff(self.seq_offsets))
-
-    def log2_affinity(self) -> np.ndarray:
-        """float64 [K, N, 2]: log2(sum) + log2_offset, NaN where the side has no window"""
-        out = np.full(self.sums.shape, np.nan)
-        some = self.sums > 0
-        out[some] = np.log2(self.sums[some].astype(np.float64)) + self.log2_offset
-        return out
+    def _shape(self):
+        return (len(self.lengths), len(self.bases), 2), "the sequences and lengths"
 
     def named_blocks(self) -> np.ndarray:
         """bool [K, N]: the block fits its sequence, its bases are non-inserted and their coordinates consecutive -- what a
@@ -223,18 +152,9 @@ class DeletionScan:
         n, k = np.nonzero(keep.T)
         return n.astype(np.int64), k.astype(np.int64)
 
-    def _numbers(self, n, k):
-        """of the cells (n, k) -> (ref best, alt best (int64, -1: none), ref p, alt p, ref log2, alt log2)"""
-        rb, ab = decode_keys(self.keys[k, n, COVER])[0], decode_keys(self.keys[k, n, DEL])[0]
-        la = lambda s: np.where(s > 0, np.log2(np.where(s > 0, s, 1).astype(np.float64)) + self.log2_offset, np.nan)   # noqa: E731
-        return (rb, ab, scaled_pvalues(rb, self.ptable), scaled_pvalues(ab, self.ptable), la(self.sums[k, n, COVER]),
-                la(self.sums[k, n, DEL]))
-
-    def _kept_cells(self):
-        n, k = self._cells()
-        rb, ab, rp, ap, rl, al = self._numbers(n, k)
-        keep = keep_rows(effect_codes(rp, ap, self.threshold), al - rl, self.delta, self.all_rows)
-        return n[keep], k[keep]
+    @staticmethod
+    def _sides(n, k):
+        return (k, n, 0), (k, n, 1)
 
     def _deleted(self, n, k) -> np.ndarray:
         """object: the deleted bases, upper case"""
@@ -245,7 +165,7 @@ class DeletionScan:
         j = np.arange(width, dtype=np.int64)[None, :]
         text = _UPPER[self.bases[np.minimum(n[:, None] + j, len(self.bases) - 1)]]
         text[j >= L[:, None]] = 0                                 # (a fixed-width byte string drops its trailing zeros)
-        return np.ascontiguousarray(text).view(f"S{width}").reshape(-1).astype(f"U{width}").astype(object)
+        return fixed_text(text)
 
     def _kmers(self, n, k, side: str) -> np.ndarray:
         """object: the best window of the side as printed ('-': reverse complemented), '' where there is none.  The REF side's
@@ -260,9 +180,7 @@ class DeletionScan:
         if side == "alt":                                         # y's base i is x's i before the block, x's i + L behind it
             at = at + np.where(at >= n[:, None], self.lengths.astype(np.int64)[k][:, None], 0)
         text = _UPPER[self.bases[np.clip(at, 0, max(len(self.bases) - 1, 0))]]
-        minus = strand == "-"
-        text[minus] = _COMP[text[minus]][:, ::-1]
-        out = np.ascontiguousarray(text).view(f"S{W}").reshape(-1).astype(f"U{W}").astype(object)
+        out = printed_windows(text, strand == "-")
         out[~some] = ""
         return out
 
@@ -276,31 +194,16 @@ class DeletionScan:
         sequence), ref_log2_affinity, alt_log2_affinity, delta_log2_affinity, effect -- NaN or empty where a side has no
         window.  Rows in (sequence, offset, length) order, the sequences by region, then version, the reference sequence last."""
         n, k = self._kept_cells()
-        rows = len(n)
-        seq = self.base_sequence[n] if rows else np.zeros(0, dtype=np.int64)
-        data = {"motif_id": np.full(rows, self.motif_id, dtype=object), "motif_alt_id": np.full(rows, self.motif_alt_id, dtype=object),
-                "sequence_name": self.region_names[self.seq_region[seq]] if rows else np.zeros(0, dtype=object),
-                "version": self.seq_version[seq], "haplotypes": self.seq_count[seq]}
-        for g, name in enumerate(self.group_names):
-            data[f"haplotypes_{name}"] = self.seq_group_counts[seq, g]
-        data["is_reference"] = self.seq_is_reference[seq]
-        co = self.coord[n].astype(np.int64)
-        data["position"] = np.where(co < 0, ~co, co) + 1
-        data["inserted"] = co < 0
+        data = self._block_columns(n, k)
+        data["deleted"] = self._deleted(n, k)
+        return self._detail_frame(n, k, data)
+
+    def _block_columns(self, n, k) -> dict:
+        """the leading columns of the blocks (n, k), then length and named"""
+        data = self._leading_columns(n)
         data["length"] = self.lengths.astype(np.int64)[k]
         data["named"] = self.named_blocks()[k, n]
-        data["deleted"] = self._deleted(n, k)
-        rb, ab, rp, ap, rl, al = self._numbers(n, k)
-        for side, best, p, col in (("ref", rb, rp, COVER), ("alt", ab, ap, DEL)):
-            _, rel, strand = decode_keys(self.keys[k, n, col])
-            data[f"{side}_score"] = scaled_scores(best, self.scale, self.offset, self.width)
-            data[f"{side}_pvalue"] = p
-            data[f"{side}_start"] = np.where(best >= 0, rel.astype(np.float64), np.nan)
-            data[f"{side}_strand"] = strand
-            data[f"{side}_kmer"] = self._kmers(n, k, side)
-        data["ref_log2_affinity"], data["alt_log2_affinity"], data["delta_log2_affinity"] = rl, al, al - rl
-        data["effect"] = EFFECTS[effect_codes(rp, ap, self.threshold)]
-        return pd.DataFrame(data)
+        return data
 
     def summary_frame(self) -> pd.DataFrame:
         """a row per (region, coordinate of the first deleted base, length) over the versions (not the count-0 reference
@@ -310,27 +213,11 @@ class DeletionScan:
         gains or loses, or when a delta is given and the smallest or largest delta reaches it; all_rows keeps everything.  Rows
         in (region, position, length) order."""
         n, k = self._cells(every=True)
-        seq = self.base_sequence[n] if len(n) else np.zeros(0, dtype=np.int64)
+        seq = self._sequence_of(n)
         on = (self.named_blocks()[k, n] & (self.seq_version[seq] >= 0)) if len(n) else np.zeros(0, dtype=bool)
         n, k, seq = n[on], k[on], seq[on]
-        rb, ab, rp, ap, rl, al = self._numbers(n, k)
-        codes = effect_codes(rp, ap, self.threshold)
-        region, length = self.seq_region[seq], self.lengths.astype(np.int64)[k]
-        first, versions, haps, gain, loss, lo, hi, best = group_summary((region, self.coord[n].astype(np.int64), length),
-                                                                        self.seq_count[seq], codes, al - rl, ab)
-        keep = np.ones(len(first), dtype=bool) if self.all_rows else (gain + loss) > 0
-        if self.delta is not None and not self.all_rows:
-            with np.errstate(invalid="ignore"):
-                keep |= (np.abs(lo) >= self.delta) | (np.abs(hi) >= self.delta)
-        j = np.flatnonzero(keep)
-        f = first[j]
-        rows = len(j)
-        return pd.DataFrame({
-            "motif_id": np.full(rows, self.motif_id, dtype=object), "motif_alt_id": np.full(rows, self.motif_alt_id, dtype=object),
-            "sequence_name": self.region_names[region[f]] if rows else np.zeros(0, dtype=object),
-            "position": self.coord[n[f]].astype(np.int64) + 1, "length": length[f], "versions": versions[j], "haplotypes": haps[j],
-            "haplotypes_gain": gain[j], "haplotypes_loss": loss[j], "min_delta_log2_affinity": lo[j],
-            "max_delta_log2_affinity": hi[j], "best_alt_score": scaled_scores(best[j], self.scale, self.offset, self.width)})
+        length = self.lengths.astype(np.int64)[k]
+        return self._summary_frame(n, k, seq, (length,), lambda f: {"length": length[f]})
 
 
 def compute_deletion_scan_many(motifs: Sequence, graph, regions, debug: bool, args_obj, lengths, chrom_names=None,
@@ -343,34 +230,14 @@ def compute_deletion_scan_many(motifs: Sequence, graph, regions, debug: bool, ar
     reference's; one kernel call per motif width (in chunks of motifs under `max_bytes`).  args_obj: noreverse and threshold
     (`threshold` overrides it).  The frames keep a row when its effect is gain or loss, or when |delta_log2_affinity| >=
     `delta` if a delta is given; `all_rows` keeps everything."""
-    from .haplotype_classes import compute_haplotype_classes
-    from .haplotype_sequences import compute_haplotype_sequences
-    require_single_gpu("the deletion scan", "is", "a gather of the sharded class matrices")
     lengths = checked_lengths(lengths)
-    if weights is not None and len(weights) != len(motifs):
-        raise ValueError(f"{len(weights)} weight tables for {len(motifs)} motifs")
-    if delta is not None and not float(delta) >= 0:
-        raise ValueError(f"delta {delta}: it must be >= 0")
-    prep = prepare_graphs(graph, regions, chrom_names)
-    _haplotype_set(prep, None, "the deletion scan")
-    rows, region_names = _matrix_rows(prep)
-    hc = compute_haplotype_classes(graph, regions, debug, args_obj, chrom_names, None, haplotype_groups)
-    hs = compute_haplotype_sequences(graph, regions, debug, args_obj, chrom_names, None, None, classes=hc, coordinates=True)
-    seqs = _with_references(hs, prep, rows)
-    seq_offsets, bases, coord = np.ascontiguousarray(seqs[5]), np.ascontiguousarray(seqs[6]), seqs[7]
-    forward_only = bool(getattr(args_obj, "noreverse", False))
-    threshold = float(args_obj.threshold if threshold is None else threshold)
-    out: List[Optional[DeletionScan]] = [None] * len(motifs)
-    for W, idxs in group_by_width(motifs).items():
-        got, offsets, numbers = _scan_chunked([motifs[i] for i in idxs], seq_offsets, bases, lengths,
-                                              None if weights is None else [weights[i] for i in idxs], temperature, forward_only,
-                                              max_bytes)
-        for m, i in enumerate(idxs):
-            scale, offset, ptable = numbers[m]
-            out[i] = DeletionScan(motifs[i].motif_id, motifs[i].motif_name, W, scale, offset, ptable, offsets[m], threshold,
-                                  region_names, hs.group_names, *seqs[:5], seq_offsets, bases, coord, lengths, got[m][0], got[m][1],
-                                  delta, all_rows)
-    return out
+    seqs, region_names, group_names, forward_only, threshold = scan_inputs(
+        "the deletion scan", motifs, graph, regions, debug, args_obj, chrom_names, haplotype_groups, weights, delta, threshold)
+    return tables_by_width(
+        motifs, weights,
+        lambda ms, ws: _scan_chunked(ms, seqs[5], seqs[6], lengths, ws, temperature, forward_only, max_bytes),
+        lambda motif, W, numbers, log2_offset, got: DeletionScan(motif.motif_id, motif.motif_name, W, *numbers, log2_offset, threshold,
+                                                                 region_names, group_names, *seqs, lengths, *got, delta, all_rows))
 
 
 def compute_deletion_scan(motif, graph, regions, debug: bool, args_obj, lengths, chrom_names=None,
@@ -382,18 +249,6 @@ def compute_deletion_scan(motif, graph, regions, debug: bool, args_obj, lengths,
                                       None if weights is None else [weights], temperature, threshold, delta, all_rows, max_bytes)[0]
 
 
-def write_deletion_scan(table: DeletionScan, motif, motif_num: int, args_obj, out=None) -> Optional[str]:
-    """grafimo_deletion_scan.tsv (grafimo_deletion_scan_<motif_id>.tsv for one of several motifs), the detail rows, in the
-    directory write_results uses for this motif -> the path written.  `out`: a text stream to write to instead (-f: stdout)."""
-    return write_frame(table.to_frame(), out if out is not None else table_path(DETAIL_FILE, args_obj, motif, motif_num))
-
-
-def write_deletion_scan_summary(table: DeletionScan, motif, motif_num: int, args_obj, out=None) -> Optional[str]:
-    """grafimo_deletion_scan_summary[_<motif_id>].tsv, a row per (region, coordinate, length), beside the detail rows"""
-    return write_frame(table.summary_frame(), out if out is not None else table_path(SUMMARY_FILE, args_obj, motif, motif_num))
-
-
-def print_deletion_scan(table: DeletionScan) -> None:
-    """-f: the detail rows, then the summary, on stdout instead of files"""
-    write_deletion_scan(table, None, 1, None, out=sys.stdout)
-    write_deletion_scan_summary(table, None, 1, None, out=sys.stdout)
+# grafimo_deletion_scan[_<motif_id>].tsv, grafimo_deletion_scan_summary[_<motif_id>].tsv (a row per (region, coordinate, length)),
+# and -f: both on stdout
+write_deletion_scan, write_deletion_scan_summary, print_deletion_scan = table_writers(DETAIL_FILE, SUMMARY_FILE)

@@ -33,17 +33,14 @@ The hot path is HIP (grafimo_amd/csrc/gfm_graph_indel_scan.hpp, gfm_sequence_ind
 scored once, and every window of the 5 n edited sequences is put together from two stored pieces.  Everything from the
 kernel's arrays to the frames is numpy group-bys; there is no Python step per row or per base.
 """
-import sys
 from typing import List, Mapping, Optional, Sequence, Tuple
 
 import numpy as np
 import pandas as pd
 
-from .graph_tables import (_haplotype_set, _matrix_rows, group_by_width, prepare_graphs, require_single_gpu, scaled_pvalues,
-                           scaled_scores, table_path, write_frame)
-from .mutation_scan import (_COMP, _UPPER, DEFAULT_MAX_BYTES, TO_BASES, _checked_sequences, _scan_chunked, _with_references,
-                            effect_codes, group_summary, keep_rows)
-from .query_variants import EFFECTS, decode_keys
+from .query_variants import decode_keys
+from .sequence_scans import (_LETTERS, _UPPER, DEFAULT_MAX_BYTES, TO_BASES, ScanTable, _checked_sequences, printed_windows,
+                             scan_chunked, scan_inputs, table_writers, tables_by_width)
 
 DETAIL_FILE = "grafimo_indel_scan"
 SUMMARY_FILE = "grafimo_indel_scan_summary"
@@ -64,7 +61,8 @@ def scan_sequences(motifs: Sequence, seq_offsets, bases, weights: Optional[Seque
     and motif) stay under `max_bytes`; a single motif above it is a ValueError that names it.  The library refuses motifs of
     two widths and weights that can overflow a sum."""
     seq_offsets, bases = _checked_sequences(seq_offsets, bases)
-    return _scan_chunked(motifs, seq_offsets, bases, weights, temperature, forward_only, max_bytes, ENTRY, len(COLUMNS))[0]
+    return scan_chunked(motifs, seq_offsets, bases, weights, temperature, forward_only, max_bytes, ENTRY,
+                        (len(bases), len(COLUMNS)))[0]
 
 
 def leftmost_changes(seq_offsets, bases) -> np.ndarray:
@@ -82,7 +80,7 @@ def leftmost_changes(seq_offsets, bases) -> np.ndarray:
     return keep
 
 
-class IndelScan:
+class IndelScan(ScanTable):
     """The table of one motif over S sequences of N bases in all (see the module's docstring).
     Per sequence [S]: seq_region, seq_version (-1: the region's reference sequence, which no haplotype spells), seq_count,
     seq_group_counts [S, G], seq_is_reference, seq_offsets int64 [S + 1] -- as MutationScan's.
@@ -90,40 +88,7 @@ class IndelScan:
     uint64 [N, 7] with the columns COVER, DEL, JUNCTION, INS_A, INS_C, INS_G, INS_T: the deletion of base n compares column 1
     with column 0, the insertion of b behind it column 3 .. 6 with column 2."""
 
-    def __init__(self, motif_id, motif_alt_id, width, scale, offset, ptable, log2_offset, threshold, region_names, group_names,
-                 seq_region, seq_version, seq_count, seq_group_counts, seq_is_reference, seq_offsets, bases, coord, keys, sums,
-                 delta=None, all_rows=False):
-        self.motif_id, self.motif_alt_id = motif_id, motif_alt_id
-        self.width, self.scale, self.offset = int(width), int(scale), float(offset)
-        self.ptable, self.log2_offset, self.threshold = np.asarray(ptable, dtype=np.float64), float(log2_offset), float(threshold)
-        self.region_names, self.group_names = np.asarray(region_names, dtype=object), list(group_names)
-        self.seq_region, self.seq_version = np.asarray(seq_region, dtype=np.int64), np.asarray(seq_version, dtype=np.int64)
-        self.seq_count = np.asarray(seq_count, dtype=np.int64)
-        self.seq_group_counts = np.asarray(seq_group_counts, dtype=np.int64).reshape(len(self.seq_count), len(self.group_names))
-        self.seq_is_reference = np.asarray(seq_is_reference, dtype=bool)
-        self.seq_offsets = np.asarray(seq_offsets, dtype=np.int64)
-        self.bases, self.coord = np.asarray(bases, dtype=np.uint8), np.asarray(coord, dtype=np.int32)
-        self.keys, self.sums = np.asarray(keys, dtype=np.uint32), np.asarray(sums, dtype=np.uint64)
-        N = len(self.bases)
-        if self.keys.shape != (N, 7) or self.sums.shape != (N, 7) or len(self.coord) != N or int(self.seq_offsets[-1]) != N:
-            raise ValueError("the arrays do not fit the sequences")
-        self.delta = None if delta is None else float(delta)
-        self.all_rows = bool(all_rows)
-
-    def __len__(self) -> int:
-        return int(self._kept_cells()[0].size)
-
-    @property
-    def base_sequence(self) -> np.ndarray:
-        """int64 [N]: the sequence of every base"""
-        return np.repeat(np.arange(len(self.seq_count), dtype=np.int64), np.diff(self.seq_offsets))
-
-    def log2_affinity(self) -> np.ndarray:
-        """float64 [N, 7]: log2(sum) + log2_offset, NaN where the side has no window"""
-        out = np.full(self.sums.shape, np.nan)
-        some = self.sums > 0
-        out[some] = np.log2(self.sums[some].astype(np.float64)) + self.log2_offset
-        return out
+    COLUMNS = COLUMNS
 
     def _cells(self):
         """every (base, change) cell the homopolymer rule keeps -> (base index n, ALT column c in 1, 3 .. 6), in (n, DEL, INS A
@@ -135,18 +100,8 @@ class IndelScan:
     def _ref_column(c):
         return np.where(c == DEL, COVER, JUNCTION)
 
-    def _numbers(self, n, c):
-        """of the cells (n, c) -> (ref best, alt best (int64, -1: none), ref p, alt p, ref log2, alt log2)"""
-        r = self._ref_column(c)
-        rb, ab = decode_keys(self.keys[n, r])[0], decode_keys(self.keys[n, c])[0]
-        la = lambda s: np.where(s > 0, np.log2(np.where(s > 0, s, 1).astype(np.float64)) + self.log2_offset, np.nan)   # noqa: E731
-        return rb, ab, scaled_pvalues(rb, self.ptable), scaled_pvalues(ab, self.ptable), la(self.sums[n, r]), la(self.sums[n, c])
-
-    def _kept_cells(self):
-        n, c = self._cells()
-        rb, ab, rp, ap, rl, al = self._numbers(n, c)
-        keep = keep_rows(effect_codes(rp, ap, self.threshold), al - rl, self.delta, self.all_rows)
-        return n[keep], c[keep]
+    def _sides(self, n, c):
+        return (n, self._ref_column(c)), (n, c)
 
     def _change_base(self, n, c) -> np.ndarray:
         """uint8: the deleted base (folded to upper case) or the inserted one"""
@@ -172,9 +127,7 @@ class IndelScan:
         if side == "alt":
             ins = np.flatnonzero(some & (c != DEL))
             text[ins, (-rel)[ins]] = TO_BASES[c[ins] - INS_A]
-        minus = strand == "-"
-        text[minus] = _COMP[text[minus]][:, ::-1]
-        out = np.ascontiguousarray(text).view(f"S{W}").reshape(-1).astype(f"U{W}").astype(object)
+        out = printed_windows(text, strand == "-")
         out[~some] = ""
         return out
 
@@ -188,31 +141,10 @@ class IndelScan:
         ref_log2_affinity, alt_log2_affinity, delta_log2_affinity, effect -- NaN or empty where a side has no window.  Rows in
         (sequence, offset, DEL, INS A C G T) order, the sequences by region, then version, the reference sequence last."""
         n, c = self._kept_cells()
-        rows = len(n)
-        seq = self.base_sequence[n] if rows else np.zeros(0, dtype=np.int64)
-        data = {"motif_id": np.full(rows, self.motif_id, dtype=object), "motif_alt_id": np.full(rows, self.motif_alt_id, dtype=object),
-                "sequence_name": self.region_names[self.seq_region[seq]] if rows else np.zeros(0, dtype=object),
-                "version": self.seq_version[seq], "haplotypes": self.seq_count[seq]}
-        for g, name in enumerate(self.group_names):
-            data[f"haplotypes_{name}"] = self.seq_group_counts[seq, g]
-        data["is_reference"] = self.seq_is_reference[seq]
-        co = self.coord[n].astype(np.int64)
-        data["position"] = np.where(co < 0, ~co, co) + 1
-        data["inserted"] = co < 0
-        letters = np.array([chr(k) for k in range(256)], dtype=object)
+        data = self._leading_columns(n)
         data["type"] = np.where(c == DEL, "DEL", "INS").astype(object)
-        data["base"] = letters[self._change_base(n, c)] if rows else np.zeros(0, dtype=object)
-        rb, ab, rp, ap, rl, al = self._numbers(n, c)
-        for side, best, p, col in (("ref", rb, rp, self._ref_column(c)), ("alt", ab, ap, c)):
-            _, rel, strand = decode_keys(self.keys[n, col])
-            data[f"{side}_score"] = scaled_scores(best, self.scale, self.offset, self.width)
-            data[f"{side}_pvalue"] = p
-            data[f"{side}_start"] = np.where(best >= 0, rel.astype(np.float64), np.nan)
-            data[f"{side}_strand"] = strand
-            data[f"{side}_kmer"] = self._kmers(n, c, side)
-        data["ref_log2_affinity"], data["alt_log2_affinity"], data["delta_log2_affinity"] = rl, al, al - rl
-        data["effect"] = EFFECTS[effect_codes(rp, ap, self.threshold)]
-        return pd.DataFrame(data)
+        data["base"] = _LETTERS[self._change_base(n, c)]
+        return self._detail_frame(n, c, data)
 
     def summary_frame(self) -> pd.DataFrame:
         """a row per (region, coordinate, type, base) over the versions (not the count-0 reference sequence) that carry that
@@ -222,29 +154,12 @@ class IndelScan:
         the smallest or largest delta reaches it; all_rows keeps everything.  Rows in (region, position, DEL before INS, base)
         order."""
         n, c = self._cells()
-        seq = self.base_sequence[n] if len(n) else np.zeros(0, dtype=np.int64)
+        seq = self._sequence_of(n)
         on = (self.coord[n] >= 0) & (self.seq_version[seq] >= 0)
         n, c, seq = n[on], c[on], seq[on]
-        rb, ab, rp, ap, rl, al = self._numbers(n, c)
-        codes = effect_codes(rp, ap, self.threshold)
-        region, kind, base = self.seq_region[seq], (c != DEL).astype(np.int64), self._change_base(n, c).astype(np.int64)
-        first, versions, haps, gain, loss, lo, hi, best = group_summary((region, self.coord[n].astype(np.int64), kind, base),
-                                                                        self.seq_count[seq], codes, al - rl, ab)
-        keep = np.ones(len(first), dtype=bool) if self.all_rows else (gain + loss) > 0
-        if self.delta is not None and not self.all_rows:
-            with np.errstate(invalid="ignore"):
-                keep |= (np.abs(lo) >= self.delta) | (np.abs(hi) >= self.delta)
-        k = np.flatnonzero(keep)
-        f = first[k]
-        letters = np.array([chr(j) for j in range(256)], dtype=object)
-        rows = len(k)
-        return pd.DataFrame({
-            "motif_id": np.full(rows, self.motif_id, dtype=object), "motif_alt_id": np.full(rows, self.motif_alt_id, dtype=object),
-            "sequence_name": self.region_names[region[f]] if rows else np.zeros(0, dtype=object),
-            "position": self.coord[n[f]].astype(np.int64) + 1, "type": np.where(kind[f] == 0, "DEL", "INS").astype(object),
-            "base": letters[base[f]] if rows else np.zeros(0, dtype=object), "versions": versions[k], "haplotypes": haps[k],
-            "haplotypes_gain": gain[k], "haplotypes_loss": loss[k], "min_delta_log2_affinity": lo[k],
-            "max_delta_log2_affinity": hi[k], "best_alt_score": scaled_scores(best[k], self.scale, self.offset, self.width)})
+        kind, base = (c != DEL).astype(np.int64), self._change_base(n, c).astype(np.int64)
+        return self._summary_frame(n, c, seq, (kind, base), lambda f: {"type": np.where(kind[f] == 0, "DEL", "INS").astype(object),
+                                                                       "base": _LETTERS[base[f]]})
 
 
 def compute_indel_scan_many(motifs: Sequence, graph, regions, debug: bool, args_obj, chrom_names=None,
@@ -256,33 +171,14 @@ def compute_indel_scan_many(motifs: Sequence, graph, regions, debug: bool, args_
     region added where no version is the reference's; one kernel call per motif width (in chunks of motifs under
     `max_bytes`).  args_obj: noreverse and threshold (`threshold` overrides it).  The frames keep a row when its effect is gain
     or loss, or when |delta_log2_affinity| >= `delta` if a delta is given; `all_rows` keeps everything."""
-    from .haplotype_classes import compute_haplotype_classes
-    from .haplotype_sequences import compute_haplotype_sequences
-    require_single_gpu("the indel scan", "is", "a gather of the sharded class matrices")
-    if weights is not None and len(weights) != len(motifs):
-        raise ValueError(f"{len(weights)} weight tables for {len(motifs)} motifs")
-    if delta is not None and not float(delta) >= 0:
-        raise ValueError(f"delta {delta}: it must be >= 0")
-    prep = prepare_graphs(graph, regions, chrom_names)
-    _haplotype_set(prep, None, "the indel scan")
-    rows, region_names = _matrix_rows(prep)
-    hc = compute_haplotype_classes(graph, regions, debug, args_obj, chrom_names, None, haplotype_groups)
-    hs = compute_haplotype_sequences(graph, regions, debug, args_obj, chrom_names, None, None, classes=hc, coordinates=True)
-    seqs = _with_references(hs, prep, rows)
-    seq_offsets, bases, coord = np.ascontiguousarray(seqs[5]), np.ascontiguousarray(seqs[6]), seqs[7]
-    forward_only = bool(getattr(args_obj, "noreverse", False))
-    threshold = float(args_obj.threshold if threshold is None else threshold)
-    out: List[Optional[IndelScan]] = [None] * len(motifs)
-    for W, idxs in group_by_width(motifs).items():
-        got, offsets, numbers = _scan_chunked([motifs[i] for i in idxs], seq_offsets, bases,
-                                              None if weights is None else [weights[i] for i in idxs], temperature, forward_only,
-                                              max_bytes, ENTRY, len(COLUMNS))
-        for m, i in enumerate(idxs):
-            scale, offset, ptable = numbers[m]
-            out[i] = IndelScan(motifs[i].motif_id, motifs[i].motif_name, W, scale, offset, ptable, offsets[m], threshold,
-                               region_names, hs.group_names, *seqs[:5], seq_offsets, bases, coord, got[m][0], got[m][1], delta,
-                               all_rows)
-    return out
+    seqs, region_names, group_names, forward_only, threshold = scan_inputs(
+        "the indel scan", motifs, graph, regions, debug, args_obj, chrom_names, haplotype_groups, weights, delta, threshold)
+    return tables_by_width(
+        motifs, weights,
+        lambda ms, ws: scan_chunked(ms, seqs[5], seqs[6], ws, temperature, forward_only, max_bytes, ENTRY,
+                                    (len(seqs[6]), len(COLUMNS))),
+        lambda motif, W, numbers, log2_offset, got: IndelScan(motif.motif_id, motif.motif_name, W, *numbers, log2_offset, threshold,
+                                                              region_names, group_names, *seqs, *got, delta, all_rows))
 
 
 def compute_indel_scan(motif, graph, regions, debug: bool, args_obj, chrom_names=None, haplotype_groups: Optional[Mapping] = None,
@@ -293,18 +189,6 @@ def compute_indel_scan(motif, graph, regions, debug: bool, args_obj, chrom_names
                                    None if weights is None else [weights], temperature, threshold, delta, all_rows, max_bytes)[0]
 
 
-def write_indel_scan(table: IndelScan, motif, motif_num: int, args_obj, out=None) -> Optional[str]:
-    """grafimo_indel_scan.tsv (grafimo_indel_scan_<motif_id>.tsv for one of several motifs), the detail rows, in the directory
-    write_results uses for this motif -> the path written.  `out`: a text stream to write to instead (-f: stdout)."""
-    return write_frame(table.to_frame(), out if out is not None else table_path(DETAIL_FILE, args_obj, motif, motif_num))
-
-
-def write_indel_scan_summary(table: IndelScan, motif, motif_num: int, args_obj, out=None) -> Optional[str]:
-    """grafimo_indel_scan_summary[_<motif_id>].tsv, a row per (region, coordinate, type, base), beside the detail rows"""
-    return write_frame(table.summary_frame(), out if out is not None else table_path(SUMMARY_FILE, args_obj, motif, motif_num))
-
-
-def print_indel_scan(table: IndelScan) -> None:
-    """-f: the detail rows, then the summary, on stdout instead of files"""
-    write_indel_scan(table, None, 1, None, out=sys.stdout)
-    write_indel_scan_summary(table, None, 1, None, out=sys.stdout)
+# grafimo_indel_scan[_<motif_id>].tsv, grafimo_indel_scan_summary[_<motif_id>].tsv (a row per (region, coordinate, type, base)),
+# and -f: both on stdout
+write_indel_scan, write_indel_scan_summary, print_indel_scan = table_writers(DETAIL_FILE, SUMMARY_FILE)

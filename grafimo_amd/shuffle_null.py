@@ -75,9 +75,8 @@ import pandas as pd
 
 from . import _native as nv
 from .extract_regions import _stream_ptr, _torch
-from .graph_tables import (_haplotype_set, _matrix_rows, group_by_width, prepare_graphs, require_single_gpu, scaled_pvalues,
-                           scaled_scores, table_path, write_frame)
-from .mutation_scan import _UPPER, DEFAULT_MAX_BYTES, _checked_sequences, _leased_chunks, _with_references
+from .graph_tables import scaled_pvalues, scaled_scores, table_path, write_frame
+from .sequence_scans import _UPPER, DEFAULT_MAX_BYTES, _checked_sequences, _leased_chunks, scan_inputs, tables_by_width
 
 TABLE_FILE = "grafimo_shuffle_null"
 ENRICHMENT_FILE = "grafimo_motif_enrichment"
@@ -201,7 +200,7 @@ def _launch(dms, tables, seq_offsets, bases, keys, seq_weights, K, seed, cuts, f
 def _null_chunked(motifs: Sequence, seq_offsets, bases, replicates, seed, seq_keys, seq_weights, cuts, threshold, weights,
                   temperature, forward_only, keep, max_bytes, order=1, walk_cap=DEFAULT_WALK_CAP):
     """-> (per motif its dict of arrays (with "cut"), per motif its log2 offset, per motif (scale, offset, ptable)): the motifs
-    leased (mutation_scan._leased_chunks) and the sequences taken in chunks whose device result tensors stay under max_bytes;
+    leased (sequence_scans._leased_chunks) and the sequences taken in chunks whose device result tensors stay under max_bytes;
     rep_hits of sequence chunks are added here.  `cuts` None: pvalue_cut at `threshold`, or L without one."""
     S, K = len(seq_offsets) - 1, int(replicates)
     if not 1 <= K <= MAX_REPLICATES:
@@ -357,37 +356,22 @@ def compute_shuffle_null_many(motifs: Sequence, graph, regions, debug: bool, arg
     `max_bytes`).  The keys are content_keys; seq_weight is 1 for each region's version 0 and 0 elsewhere (enrichment_frame says
     why); the cut is pvalue_cut at the threshold.  args_obj: noreverse and threshold (`threshold` overrides it).
     `temperature` / `weights` as compute_haplotype_affinity_many's.  `order`: 1, or 2 for doublet-preserving replicates."""
-    from .haplotype_classes import compute_haplotype_classes
-    from .haplotype_sequences import compute_haplotype_sequences
-    require_single_gpu("the shuffle null", "is", "a gather of the sharded class matrices")
-    if weights is not None and len(weights) != len(motifs):
-        raise ValueError(f"{len(weights)} weight tables for {len(motifs)} motifs")
     if not 1 <= int(replicates) <= MAX_REPLICATES:
         raise ValueError(f"replicates {replicates}: outside [1, {MAX_REPLICATES}]")
     order = _checked_order(order)[0]
-    prep = prepare_graphs(graph, regions, chrom_names)
-    _haplotype_set(prep, None, "the shuffle null")
-    rows, region_names = _matrix_rows(prep)
-    hc = compute_haplotype_classes(graph, regions, debug, args_obj, chrom_names, None, haplotype_groups)
-    hs = compute_haplotype_sequences(graph, regions, debug, args_obj, chrom_names, None, None, classes=hc, coordinates=True)
-    seqs = _with_references(hs, prep, rows)
-    seq_offsets, bases = np.ascontiguousarray(seqs[5]), np.ascontiguousarray(seqs[6])
+    seqs, region_names, group_names, forward_only, threshold = scan_inputs(
+        "the shuffle null", motifs, graph, regions, debug, args_obj, chrom_names, haplotype_groups, weights, None, threshold)
+    seq_offsets, bases = seqs[5], seqs[6]
     seq_weight = (np.asarray(seqs[1]) == 0).astype(np.uint32)
     keys = content_keys(seq_offsets, bases)
-    forward_only = bool(getattr(args_obj, "noreverse", False))
-    threshold = float(args_obj.threshold if threshold is None else threshold)
-    out: List[Optional[ShuffleNull]] = [None] * len(motifs)
-    for W, idxs in group_by_width(motifs).items():
-        got, offsets, numbers = _null_chunked([motifs[i] for i in idxs], seq_offsets, bases, replicates, seed, keys, seq_weight, None,
-                                              threshold, None if weights is None else [weights[i] for i in idxs], temperature,
-                                              forward_only, False, max_bytes, order)
-        for m, i in enumerate(idxs):
-            scale, offset, ptable = numbers[m]
-            g = got[m]
-            out[i] = ShuffleNull(motifs[i].motif_id, motifs[i].motif_name, W, scale, offset, ptable, offsets[m], threshold,
-                                 region_names, hs.group_names, *seqs[:5], np.diff(seq_offsets), seq_weight, replicates, seed,
-                                 g["obs_best"], g["obs_sum"], g["ge_best"], g["ge_sum"], g["rep_hits"], g["cut"], order)
-    return out
+    return tables_by_width(
+        motifs, weights,
+        lambda ms, ws: _null_chunked(ms, seq_offsets, bases, replicates, seed, keys, seq_weight, None, threshold, ws, temperature,
+                                     forward_only, False, max_bytes, order),
+        lambda motif, W, numbers, log2_offset, g: ShuffleNull(
+            motif.motif_id, motif.motif_name, W, *numbers, log2_offset, threshold, region_names, group_names, *seqs[:5],
+            np.diff(seq_offsets), seq_weight, replicates, seed, g["obs_best"], g["obs_sum"], g["ge_best"], g["ge_sum"], g["rep_hits"],
+            g["cut"], order))
 
 
 def compute_shuffle_null(motif, graph, regions, debug: bool, args_obj, chrom_names=None, haplotype_groups: Optional[Mapping] = None,

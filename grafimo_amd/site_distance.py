@@ -40,7 +40,6 @@ selection in registers.  Everything from the kernel's arrays to the frames is nu
 or per base.
 """
 import ctypes
-import sys
 from typing import List, Mapping, Optional, Sequence, Tuple
 
 import numpy as np
@@ -48,9 +47,9 @@ import pandas as pd
 
 from . import _native as nv
 from .extract_regions import _stream_ptr, _torch
-from .graph_tables import (_haplotype_set, _matrix_rows, group_by_width, prepare_graphs, require_single_gpu, scaled_pvalues,
-                           scaled_scores, table_path, write_frame)
-from .mutation_scan import _COMP, _UPPER, DEFAULT_MAX_BYTES, TO_BASES, _checked_sequences, _with_references
+from .graph_tables import scaled_pvalues, scaled_scores
+from .sequence_scans import (_UPPER, DEFAULT_MAX_BYTES, TO_BASES, SequenceTable, _checked_sequences, chunk_step, printed_windows,
+                             scan_inputs, table_writers, tables_by_width)
 
 DETAIL_FILE = "grafimo_site_distance"
 SUMMARY_FILE = "grafimo_site_distance_summary"
@@ -128,11 +127,7 @@ def _scan_chunked(motifs: Sequence, seq_offsets, bases, cutoffs, threshold, max_
     max_edits = checked_edits(max_edits)
     if cutoffs is not None and len(cutoffs) != len(motifs):
         raise ValueError(f"{len(cutoffs)} cutoffs for {len(motifs)} motifs")
-    per_motif = BYTES_PER_BASE * int(seq_offsets[-1])
-    if per_motif > int(max_bytes):
-        raise ValueError(f"{motifs[0].motif_id}: the words and masks of one motif over {int(seq_offsets[-1])} bases hold {per_motif} "
-                         f"bytes, more than max_bytes = {int(max_bytes)}: scan fewer sequences at a time, or raise max_bytes")
-    step = max(1, int(max_bytes) // max(per_motif, 1))
+    step = chunk_step(motifs, int(seq_offsets[-1]), BYTES_PER_BASE * int(seq_offsets[-1]), max_bytes, "words and masks")
     results, used, numbers = [], [], []
     for m0 in range(0, len(motifs), step):
         dms = [DeviceMotif.lease(m) for m in motifs[m0:m0 + step]]
@@ -180,7 +175,7 @@ def _group_heads(keys: Sequence[np.ndarray]):
     return order, np.flatnonzero(head)
 
 
-class SiteDistance:
+class SiteDistance(SequenceTable):
     """The table of one motif over S sequences of N bases in all (see the module's docstring).
     Per sequence [S]: seq_region, seq_version (-1: the region's reference sequence, which no haplotype spells), seq_count
     (haplotypes), seq_group_counts [S, G], seq_is_reference, seq_offsets int64 [S + 1] -- MutationScan's.
@@ -191,32 +186,17 @@ class SiteDistance:
     def __init__(self, motif_id, motif_alt_id, width, scale, offset, ptable, tables, cutoff, max_edits, threshold, region_names,
                  group_names, seq_region, seq_version, seq_count, seq_group_counts, seq_is_reference, seq_offsets, bases, coord,
                  words, masks, all_rows=False):
-        self.motif_id, self.motif_alt_id = motif_id, motif_alt_id
-        self.width, self.scale, self.offset = int(width), int(scale), float(offset)
-        self.ptable, self.threshold = np.asarray(ptable, dtype=np.float64), float(threshold)
+        super().__init__(motif_id, motif_alt_id, width, scale, offset, ptable, threshold, region_names, group_names, seq_region,
+                         seq_version, seq_count, seq_group_counts, seq_is_reference, seq_offsets, bases, coord, all_rows)
         self.tables = np.asarray(tables, dtype=np.int64)
         self.cutoff, self.max_edits = int(cutoff), checked_edits(max_edits)
-        self.region_names, self.group_names = np.asarray(region_names, dtype=object), list(group_names)
-        self.seq_region, self.seq_version = np.asarray(seq_region, dtype=np.int64), np.asarray(seq_version, dtype=np.int64)
-        self.seq_count = np.asarray(seq_count, dtype=np.int64)
-        self.seq_group_counts = np.asarray(seq_group_counts, dtype=np.int64).reshape(len(self.seq_count), len(self.group_names))
-        self.seq_is_reference = np.asarray(seq_is_reference, dtype=bool)
-        self.seq_offsets = np.asarray(seq_offsets, dtype=np.int64)
-        self.bases, self.coord = np.asarray(bases, dtype=np.uint8), np.asarray(coord, dtype=np.int32)
         self.words, self.masks = np.asarray(words, dtype=np.uint32), np.asarray(masks, dtype=np.uint64)
         N = len(self.bases)
-        if (self.words.shape != (N, 6) or self.masks.shape != (N, 4) or len(self.coord) != N or int(self.seq_offsets[-1]) != N
-                or self.tables.shape != (2, self.width, 4)):
+        if not self._fits((self.words, (N, 6)), (self.masks, (N, 4)), (self.tables, (2, self.width, 4))):
             raise ValueError("the arrays do not fit the sequences")
-        self.all_rows = bool(all_rows)
 
     def __len__(self) -> int:
         return int(self._kept()[0].size)
-
-    @property
-    def base_sequence(self) -> np.ndarray:
-        """int64 [N]: the sequence of every base"""
-        return np.repeat(np.arange(len(self.seq_count), dtype=np.int64), np.diff(self.seq_offsets))
 
     # ---- per window-strand
     def _window_strands(self):
@@ -285,13 +265,7 @@ class SiteDistance:
         for k in range(int(rank.max()) + 1 if len(rank) else 0):                         # (at most E turns, not one per row)
             sel = rank == k
             changes[r[sel]] = np.char.add(changes[r[sel]], np.char.add("," if k else "", piece[sel]))
-        minus = st == 1
-        out = []
-        for t in (text, edited):
-            t = t.copy()
-            t[minus] = _COMP[t[minus]][:, ::-1]
-            out.append(np.ascontiguousarray(t).view(f"S{W}").reshape(-1).astype(f"U{W}").astype(object))
-        return out[0], changes.astype(object), out[1]
+        return printed_windows(text.copy(), st == 1), changes.astype(object), printed_windows(edited.copy(), st == 1)
 
     def to_frame(self) -> pd.DataFrame:
         """a row per (sequence, window start, strand) that is a site or a near-site (1 <= near d <= E); all_rows keeps every
@@ -303,18 +277,8 @@ class SiteDistance:
         1-based and forward in the window, the bases forward-strand), edited_kmer (as printed), edited_score, edited_pvalue.
         Rows in (sequence, window start, + before -) order, the sequences by region, then version, the reference sequence last."""
         n, st = self._kept()
-        rows = len(n)
         own, site, d, after, mask = self._numbers(n, st)
-        seq = self.base_sequence[n] if rows else np.zeros(0, dtype=np.int64)
-        data = {"motif_id": np.full(rows, self.motif_id, dtype=object), "motif_alt_id": np.full(rows, self.motif_alt_id, dtype=object),
-                "sequence_name": self.region_names[self.seq_region[seq]] if rows else np.zeros(0, dtype=object),
-                "version": self.seq_version[seq], "haplotypes": self.seq_count[seq]}
-        for g, name in enumerate(self.group_names):
-            data[f"haplotypes_{name}"] = self.seq_group_counts[seq, g]
-        data["is_reference"] = self.seq_is_reference[seq]
-        co = self.coord[n].astype(np.int64)
-        data["position"] = np.where(co < 0, ~co, co) + 1
-        data["inserted"] = co < 0
+        data = self._leading_columns(n)
         data["strand"] = np.array(["+", "-"], dtype=object)[st]
         kmer, changes, edited = self._texts(n, st, site, mask)
         data["kmer"] = kmer
@@ -338,7 +302,7 @@ class SiteDistance:
         order."""
         E = self.max_edits
         n, st = self._window_strands()
-        seq = self.base_sequence[n] if len(n) else np.zeros(0, dtype=np.int64)
+        seq = self._sequence_of(n)
         on = (self.coord[n] >= 0) & (self.seq_version[seq] >= 0)
         n, st, seq = n[on], st[on], seq[on]
         own, site, d, _, _ = self._numbers(n, st)
@@ -359,11 +323,9 @@ class SiteDistance:
         keep = np.ones(len(at), dtype=bool) if self.all_rows else (h_site + sum(h_near, np.zeros(len(at), dtype=np.int64))) > 0
         k = np.flatnonzero(keep)
         f = order[at[k]] if len(at) else np.zeros(0, dtype=np.int64)
-        rows = len(k)
-        data = {"motif_id": np.full(rows, self.motif_id, dtype=object), "motif_alt_id": np.full(rows, self.motif_alt_id, dtype=object),
-                "sequence_name": self.region_names[region[f]] if rows else np.zeros(0, dtype=object), "position": co[f] + 1,
-                "strand": np.array(["+", "-"], dtype=object)[st[f]], "versions": add(np.ones(len(n), dtype=np.int64))[k],
-                "haplotypes": add(haps)[k], "haplotypes_site": h_site[k]}
+        data = self._motif_columns(len(k), region[f])
+        data.update({"position": co[f] + 1, "strand": np.array(["+", "-"], dtype=object)[st[f]],
+                     "versions": add(np.ones(len(n), dtype=np.int64))[k], "haplotypes": add(haps)[k], "haplotypes_site": h_site[k]})
         for name, h in zip(names, h_near):
             data[name] = h[k]
         data["haplotypes_far"] = h_far[k]
@@ -381,29 +343,14 @@ def compute_site_distance_many(motifs: Sequence, graph, regions, debug: bool, ar
     reference's.  One kernel call per motif width (in chunks of motifs under `max_bytes`).  args_obj: noreverse and threshold
     (`threshold` overrides it); a motif's cutoff is cutoff_of its tail table at the threshold.  `max_edits`: the cap E in
     1 .. 8.  The frames keep the sites and the near-sites; `all_rows` keeps every window-strand."""
-    from .haplotype_classes import compute_haplotype_classes
-    from .haplotype_sequences import compute_haplotype_sequences
     max_edits = checked_edits(max_edits)
-    require_single_gpu("the site distance", "is", "a gather of the sharded class matrices")
-    prep = prepare_graphs(graph, regions, chrom_names)
-    _haplotype_set(prep, None, "the site distance")
-    rows, region_names = _matrix_rows(prep)
-    hc = compute_haplotype_classes(graph, regions, debug, args_obj, chrom_names, None, haplotype_groups)
-    hs = compute_haplotype_sequences(graph, regions, debug, args_obj, chrom_names, None, None, classes=hc, coordinates=True)
-    seqs = _with_references(hs, prep, rows)
-    seq_offsets, bases, coord = np.ascontiguousarray(seqs[5]), np.ascontiguousarray(seqs[6]), seqs[7]
-    forward_only = bool(getattr(args_obj, "noreverse", False))
-    threshold = float(args_obj.threshold if threshold is None else threshold)
-    out: List[Optional[SiteDistance]] = [None] * len(motifs)
-    for W, idxs in group_by_width(motifs).items():
-        got, cutoffs, numbers = _scan_chunked([motifs[i] for i in idxs], seq_offsets, bases, None, threshold, max_edits,
-                                              forward_only, max_bytes)
-        for m, i in enumerate(idxs):
-            scale, offset, ptable = numbers[m]
-            out[i] = SiteDistance(motifs[i].motif_id, motifs[i].motif_name, W, scale, offset, ptable, strand_tables(motifs[i]),
-                                  cutoffs[m], max_edits, threshold, region_names, hs.group_names, *seqs[:5], seq_offsets, bases,
-                                  coord, got[m][0], got[m][1], all_rows)
-    return out
+    seqs, region_names, group_names, forward_only, threshold = scan_inputs(
+        "the site distance", motifs, graph, regions, debug, args_obj, chrom_names, haplotype_groups, None, None, threshold)
+    return tables_by_width(
+        motifs, None,
+        lambda ms, _: _scan_chunked(ms, seqs[5], seqs[6], None, threshold, max_edits, forward_only, max_bytes),
+        lambda motif, W, numbers, cutoff, got: SiteDistance(motif.motif_id, motif.motif_name, W, *numbers, strand_tables(motif), cutoff,
+                                                            max_edits, threshold, region_names, group_names, *seqs, *got, all_rows))
 
 
 def compute_site_distance(motif, graph, regions, debug: bool, args_obj, chrom_names=None, haplotype_groups: Optional[Mapping] = None,
@@ -414,19 +361,6 @@ def compute_site_distance(motif, graph, regions, debug: bool, args_obj, chrom_na
                                       all_rows, max_bytes)[0]
 
 
-# ---------------------------------------------------------------------------------------------------------------- the writers
-def write_site_distance(table: SiteDistance, motif, motif_num: int, args_obj, out=None) -> Optional[str]:
-    """grafimo_site_distance.tsv (grafimo_site_distance_<motif_id>.tsv for one of several motifs), the detail rows, in the
-    directory write_results uses for this motif -> the path written.  `out`: a text stream to write to instead (-f: stdout)."""
-    return write_frame(table.to_frame(), out if out is not None else table_path(DETAIL_FILE, args_obj, motif, motif_num))
-
-
-def write_site_distance_summary(table: SiteDistance, motif, motif_num: int, args_obj, out=None) -> Optional[str]:
-    """grafimo_site_distance_summary[_<motif_id>].tsv, a row per (region, coordinate, strand), beside the detail rows"""
-    return write_frame(table.summary_frame(), out if out is not None else table_path(SUMMARY_FILE, args_obj, motif, motif_num))
-
-
-def print_site_distance(table: SiteDistance) -> None:
-    """-f: the detail rows, then the summary, on stdout instead of files"""
-    write_site_distance(table, None, 1, None, out=sys.stdout)
-    write_site_distance_summary(table, None, 1, None, out=sys.stdout)
+# grafimo_site_distance[_<motif_id>].tsv, grafimo_site_distance_summary[_<motif_id>].tsv (a row per (region, coordinate, strand)),
+# and -f: both on stdout
+write_site_distance, write_site_distance_summary, print_site_distance = table_writers(DETAIL_FILE, SUMMARY_FILE)

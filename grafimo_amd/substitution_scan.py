@@ -38,22 +38,16 @@ a sequence is scored once, over x and over f(x), for all lengths, and every wind
 from stored pieces.  Everything from the kernel's arrays to the frames is numpy group-bys; there is no Python step per row or
 per base.
 """
-import contextlib
-import ctypes
-import sys
 from typing import List, Mapping, Optional, Sequence, Tuple
 
 import numpy as np
 import pandas as pd
 
 from . import _native as nv
-from .deletion_scan import BYTES_PER_CELL, DeletionScan, _within, checked_lengths
-from .extract_regions import _stream_ptr, _torch
-from .graph_tables import (_haplotype_set, _matrix_rows, group_by_width, prepare_graphs, require_single_gpu, scaled_scores,
-                           table_path, write_frame)
-from .mutation_scan import (_COLUMN_OF, _COMP, _UPPER, DEFAULT_MAX_BYTES, TO_BASES, _checked_sequences, _leased_chunks,
-                            _with_references, effect_codes)
-from .query_variants import EFFECTS, decode_keys
+from .deletion_scan import DeletionScan, _scan_chunked, checked_lengths
+from .query_variants import decode_keys
+from .sequence_scans import (_COLUMN_OF, _UPPER, DEFAULT_MAX_BYTES, TO_BASES, _checked_sequences, _within, fixed_text,
+                             printed_windows, scan_inputs, table_writers, tables_by_width)
 
 DETAIL_FILE = "grafimo_substitution_scan"
 SUMMARY_FILE = "grafimo_substitution_scan_summary"
@@ -106,49 +100,6 @@ def changed_bases(seq_offsets, bases, lengths, base_map) -> np.ndarray:
 
 
 # ---------------------------------------------------------------------------------------------------------------- the kernel
-def _scan(dms, tables, seq_offsets: np.ndarray, bases: np.ndarray, lengths: np.ndarray, base_map: np.ndarray, forward_only: bool):
-    """gfm_sequence_substitution_scan for leased motifs of one width -> (keys uint32 [M, n_lengths, N, 2], sums uint64 of that
-    shape)"""
-    M, N, K = len(dms), int(seq_offsets[-1]), len(lengths)
-    if N == 0:
-        return np.zeros((M, K, 0, 2), dtype=np.uint32), np.zeros((M, K, 0, 2), dtype=np.uint64)
-    torch = _torch()
-    dev = torch.device("cuda", torch.cuda.current_device())
-    d_bases = torch.from_numpy(np.array(bases, dtype=np.uint8)).to(dev)              # (a copy: the caller's may be read-only)
-    d_tabs = [torch.from_numpy(np.ascontiguousarray(t, dtype=np.uint64).view(np.int64)).to(dev) for t in tables]
-    keys = torch.empty((M, K, N, 2), dtype=torch.int32, device=dev)
-    sums = torch.empty((M, K, N, 2), dtype=torch.int64, device=dev)
-    status = torch.zeros(1, dtype=torch.int32, device=dev)
-    vp = ctypes.c_void_p
-    nv.check(getattr(nv.lib(), ENTRY)(
-        (vp * M)(*[x.handle for x in dms]), M, (vp * M)(*[t.data_ptr() for t in d_tabs]), max(int(t.max()) for t in tables),
-        len(seq_offsets) - 1, seq_offsets.ctypes.data, d_bases.data_ptr(), K, lengths.ctypes.data, base_map.ctypes.data,
-        nv.GFM_GRAPH_FORWARD_ONLY if forward_only else 0, (vp * M)(*[keys[m].data_ptr() for m in range(M)]),
-        (vp * M)(*[sums[m].data_ptr() for m in range(M)]), status.data_ptr(), _stream_ptr(None)))
-    return keys.cpu().numpy().view(np.uint32), sums.cpu().numpy().view(np.uint64)
-
-
-def _scan_chunked(motifs: Sequence, seq_offsets, bases, lengths, base_map, weights, temperature, forward_only, max_bytes):
-    """-> (per motif (keys, sums), per motif its log2 offset, per motif (scale, offset, ptable)): the motifs leased and scanned
-    in chunks whose result tensors (24 bytes a base, length and motif) stay under max_bytes"""
-    if weights is not None and len(weights) != len(motifs):
-        raise ValueError(f"{len(weights)} weight tables for {len(motifs)} motifs")
-    per_motif = BYTES_PER_CELL * len(lengths) * int(seq_offsets[-1])
-    if per_motif > int(max_bytes):
-        raise ValueError(f"{motifs[0].motif_id}: the keys and sums of one motif over {int(seq_offsets[-1])} bases and "
-                         f"{len(lengths)} lengths hold {per_motif} bytes, more than max_bytes = {int(max_bytes)}: scan fewer "
-                         f"sequences or lengths at a time, or raise max_bytes")
-    step = max(1, int(max_bytes) // max(per_motif, 1))
-    results, offsets, numbers = [], [], []
-    with contextlib.closing(_leased_chunks(motifs, weights, temperature, step)) as chunks:     # (a failure gives the handles back)
-        for _, dms, tables, offs, nums in chunks:
-            keys, sums = _scan(dms, tables, seq_offsets, bases, lengths, base_map, forward_only)
-            results += [(keys[m], sums[m]) for m in range(len(dms))]
-            offsets += offs
-            numbers += nums
-    return results, offsets, numbers
-
-
 def scan_sequences(motifs: Sequence, seq_offsets, bases, lengths, base_map, weights: Optional[Sequence[np.ndarray]] = None,
                    temperature: float = 1.0, forward_only: bool = False,
                    max_bytes: int = DEFAULT_MAX_BYTES) -> List[Tuple[np.ndarray, np.ndarray]]:
@@ -161,7 +112,8 @@ def scan_sequences(motifs: Sequence, seq_offsets, bases, lengths, base_map, weig
     a bad map, before the library is called.  The library refuses motifs of two widths and weights that can overflow a sum."""
     lengths, base_map = checked_lengths(lengths), checked_map(base_map)
     seq_offsets, bases = _checked_sequences(seq_offsets, bases)
-    return _scan_chunked(motifs, seq_offsets, bases, lengths, base_map, weights, temperature, forward_only, max_bytes)[0]
+    return _scan_chunked(motifs, seq_offsets, bases, lengths, weights, temperature, forward_only, max_bytes, ENTRY,
+                         (base_map.ctypes.data,))[0]
 
 
 # ---------------------------------------------------------------------------------------------------------------- the table
@@ -205,9 +157,7 @@ class SubstitutionScan(DeletionScan):
         if side == "alt":                                         # y's base i is f(x[i]) inside the block, x's elsewhere
             block = (at >= n[:, None]) & (at < (n + self.lengths.astype(np.int64)[k])[:, None])
             text = np.where(block, mapped_bases(self.bases, self.base_map)[inside], text)
-        minus = strand == "-"
-        text[minus] = _COMP[text[minus]][:, ::-1]
-        out = np.ascontiguousarray(text).view(f"S{W}").reshape(-1).astype(f"U{W}").astype(object)
+        out = printed_windows(text, strand == "-")
         out[~some] = ""
         return out
 
@@ -220,7 +170,7 @@ class SubstitutionScan(DeletionScan):
         j = np.arange(width, dtype=np.int64)[None, :]
         text = mapped_bases(self.bases, self.base_map)[np.minimum(n[:, None] + j, len(self.bases) - 1)]
         text[j >= L[:, None]] = 0                                 # (a fixed-width byte string drops its trailing zeros)
-        return np.ascontiguousarray(text).view(f"S{width}").reshape(-1).astype(f"U{width}").astype(object)
+        return fixed_text(text)
 
     def to_frame(self) -> pd.DataFrame:
         """a row per (region, version, offset, length) the filter keeps (mutation_scan.keep_rows) whose block changes a base:
@@ -233,34 +183,12 @@ class SubstitutionScan(DeletionScan):
         ref_log2_affinity, alt_log2_affinity, delta_log2_affinity, effect -- NaN or empty where a side has no window.  Rows in
         (sequence, offset, length) order, the sequences by region, then version, the reference sequence last."""
         n, k = self._kept_cells()
-        rows = len(n)
-        seq = self.base_sequence[n] if rows else np.zeros(0, dtype=np.int64)
-        data = {"motif_id": np.full(rows, self.motif_id, dtype=object), "motif_alt_id": np.full(rows, self.motif_alt_id, dtype=object),
-                "sequence_name": self.region_names[self.seq_region[seq]] if rows else np.zeros(0, dtype=object),
-                "version": self.seq_version[seq], "haplotypes": self.seq_count[seq]}
-        for g, name in enumerate(self.group_names):
-            data[f"haplotypes_{name}"] = self.seq_group_counts[seq, g]
-        data["is_reference"] = self.seq_is_reference[seq]
-        co = self.coord[n].astype(np.int64)
-        data["position"] = np.where(co < 0, ~co, co) + 1
-        data["inserted"] = co < 0
-        data["length"] = self.lengths.astype(np.int64)[k]
-        data["named"] = self.named_blocks()[k, n]
-        data["map"] = np.full(rows, map_letters(self.base_map), dtype=object)
+        data = self._block_columns(n, k)
+        data["map"] = np.full(len(n), map_letters(self.base_map), dtype=object)
         data["replaced"] = self._deleted(n, k)
         data["replacement"] = self._replacement(n, k)
         data["changed"] = self.changed()[k, n].astype(np.int64)
-        rb, ab, rp, ap, rl, al = self._numbers(n, k)
-        for side, best, p, col in (("ref", rb, rp, COVER), ("alt", ab, ap, SUB)):
-            _, rel, strand = decode_keys(self.keys[k, n, col])
-            data[f"{side}_score"] = scaled_scores(best, self.scale, self.offset, self.width)
-            data[f"{side}_pvalue"] = p
-            data[f"{side}_start"] = np.where(best >= 0, rel.astype(np.float64), np.nan)
-            data[f"{side}_strand"] = strand
-            data[f"{side}_kmer"] = self._kmers(n, k, side)
-        data["ref_log2_affinity"], data["alt_log2_affinity"], data["delta_log2_affinity"] = rl, al, al - rl
-        data["effect"] = EFFECTS[effect_codes(rp, ap, self.threshold)]
-        return pd.DataFrame(data)
+        return self._detail_frame(n, k, data)
 
     def summary_frame(self) -> pd.DataFrame:
         """a row per (region, coordinate of the block's first base, length) over the versions (not the count-0 reference
@@ -281,34 +209,16 @@ def compute_substitution_scan_many(motifs: Sequence, graph, regions, debug: bool
     region added where no version is the reference's; one kernel call per motif width (in chunks of motifs under `max_bytes`).
     args_obj: noreverse and threshold (`threshold` overrides it).  The frames keep a row when its effect is gain or loss, or
     when |delta_log2_affinity| >= `delta` if a delta is given; `all_rows` keeps everything."""
-    from .haplotype_classes import compute_haplotype_classes
-    from .haplotype_sequences import compute_haplotype_sequences
     lengths, base_map = checked_lengths(lengths), checked_map(base_map)
-    require_single_gpu("the substitution scan", "is", "a gather of the sharded class matrices")
-    if weights is not None and len(weights) != len(motifs):
-        raise ValueError(f"{len(weights)} weight tables for {len(motifs)} motifs")
-    if delta is not None and not float(delta) >= 0:
-        raise ValueError(f"delta {delta}: it must be >= 0")
-    prep = prepare_graphs(graph, regions, chrom_names)
-    _haplotype_set(prep, None, "the substitution scan")
-    rows, region_names = _matrix_rows(prep)
-    hc = compute_haplotype_classes(graph, regions, debug, args_obj, chrom_names, None, haplotype_groups)
-    hs = compute_haplotype_sequences(graph, regions, debug, args_obj, chrom_names, None, None, classes=hc, coordinates=True)
-    seqs = _with_references(hs, prep, rows)
-    seq_offsets, bases, coord = np.ascontiguousarray(seqs[5]), np.ascontiguousarray(seqs[6]), seqs[7]
-    forward_only = bool(getattr(args_obj, "noreverse", False))
-    threshold = float(args_obj.threshold if threshold is None else threshold)
-    out: List[Optional[SubstitutionScan]] = [None] * len(motifs)
-    for W, idxs in group_by_width(motifs).items():
-        got, offsets, numbers = _scan_chunked([motifs[i] for i in idxs], seq_offsets, bases, lengths, base_map,
-                                              None if weights is None else [weights[i] for i in idxs], temperature, forward_only,
-                                              max_bytes)
-        for m, i in enumerate(idxs):
-            scale, offset, ptable = numbers[m]
-            out[i] = SubstitutionScan(motifs[i].motif_id, motifs[i].motif_name, W, scale, offset, ptable, offsets[m], threshold,
-                                      region_names, hs.group_names, *seqs[:5], seq_offsets, bases, coord, lengths, base_map,
-                                      got[m][0], got[m][1], delta, all_rows)
-    return out
+    seqs, region_names, group_names, forward_only, threshold = scan_inputs(
+        "the substitution scan", motifs, graph, regions, debug, args_obj, chrom_names, haplotype_groups, weights, delta, threshold)
+    return tables_by_width(
+        motifs, weights,
+        lambda ms, ws: _scan_chunked(ms, seqs[5], seqs[6], lengths, ws, temperature, forward_only, max_bytes, ENTRY,
+                                     (base_map.ctypes.data,)),
+        lambda motif, W, numbers, log2_offset, got: SubstitutionScan(motif.motif_id, motif.motif_name, W, *numbers, log2_offset,
+                                                                     threshold, region_names, group_names, *seqs, lengths, base_map,
+                                                                     *got, delta, all_rows))
 
 
 def compute_substitution_scan(motif, graph, regions, debug: bool, args_obj, lengths, base_map="transversion", chrom_names=None,
@@ -321,18 +231,6 @@ def compute_substitution_scan(motif, graph, regions, debug: bool, args_obj, leng
                                           max_bytes)[0]
 
 
-def write_substitution_scan(table: SubstitutionScan, motif, motif_num: int, args_obj, out=None) -> Optional[str]:
-    """grafimo_substitution_scan.tsv (grafimo_substitution_scan_<motif_id>.tsv for one of several motifs), the detail rows, in
-    the directory write_results uses for this motif -> the path written.  `out`: a text stream to write to instead (-f: stdout)."""
-    return write_frame(table.to_frame(), out if out is not None else table_path(DETAIL_FILE, args_obj, motif, motif_num))
-
-
-def write_substitution_scan_summary(table: SubstitutionScan, motif, motif_num: int, args_obj, out=None) -> Optional[str]:
-    """grafimo_substitution_scan_summary[_<motif_id>].tsv, a row per (region, coordinate, length), beside the detail rows"""
-    return write_frame(table.summary_frame(), out if out is not None else table_path(SUMMARY_FILE, args_obj, motif, motif_num))
-
-
-def print_substitution_scan(table: SubstitutionScan) -> None:
-    """-f: the detail rows, then the summary, on stdout instead of files"""
-    write_substitution_scan(table, None, 1, None, out=sys.stdout)
-    write_substitution_scan_summary(table, None, 1, None, out=sys.stdout)
+# grafimo_substitution_scan[_<motif_id>].tsv, grafimo_substitution_scan_summary[_<motif_id>].tsv (a row per (region, coordinate,
+# length)), and -f: both on stdout
+write_substitution_scan, write_substitution_scan_summary, print_substitution_scan = table_writers(DETAIL_FILE, SUMMARY_FILE)

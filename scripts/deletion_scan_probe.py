@@ -52,7 +52,7 @@ def main():
     from grafimo_amd import _native as nv
     from grafimo_amd import deletion_scan as dsc
     from grafimo_amd import indel_scan as isc
-    from grafimo_amd import mutation_scan as ms
+    from grafimo_amd import sequence_scans as ss
     from grafimo_amd import query_variants as qv
     from grafimo_amd import synth
     from grafimo_amd.device import DeviceMotif
@@ -123,8 +123,8 @@ def main():
                      f"is below the baseline's fastest: {below}; {Q * n_motifs / new[0] / 1e6:.3f} G deletions/s; the two agree on "
                      f"every item: {same}")
         if tuple(lengths) == (1,):
-            staged = ms._stage(tables, seq_offsets, bases, len(isc.COLUMNS))
-            floor = _timed(lambda: ms._enqueue(dms, staged, False, isc.ENTRY), a.warmup, a.reps)
+            staged = ss.stage(tables, seq_offsets, bases, (N, len(isc.COLUMNS)))
+            floor = _timed(lambda: ss.enqueue(dms, staged, False, isc.ENTRY), a.warmup, a.reps)
             cols = [isc.COVER, isc.DEL]
             equal = bool((staged[4][:, :, cols] == keys[:, 0]).all()) and bool((staged[5][:, :, cols] == sums[:, 0]).all())
             lines.append(f"lengths (1,): gfm_sequence_indel_scan on the same input (seven columns a base): median {floor[0]:.3f} ms (min "

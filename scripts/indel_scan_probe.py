@@ -55,7 +55,7 @@ def main():
     import numpy as np
     import torch
     from grafimo_amd import indel_scan as isc
-    from grafimo_amd import mutation_scan as ms
+    from grafimo_amd import sequence_scans as ss
     from grafimo_amd import query_variants as qv
     from grafimo_amd import synth
     from grafimo_amd.device import DeviceMotif
@@ -74,13 +74,13 @@ def main():
     hc = compute_haplotype_classes(dg, regions, False, _Args())
     hs = compute_haplotype_sequences(dg, regions, False, _Args(), classes=hc, coordinates=True)
     prep = prepare_graphs(dg, regions, None)
-    seqs = ms._with_references(hs, prep, _matrix_rows(prep)[0])
+    seqs = ss._with_references(hs, prep, _matrix_rows(prep)[0])
     seq_offsets, bases, coord = np.ascontiguousarray(seqs[5]), np.ascontiguousarray(seqs[6]), seqs[7]
     V, N = len(seq_offsets) - 1, len(bases)
     lines.append(f"input: {len(hs)} versions + {V - len(hs)} reference sequences = {V} sequences, {N} bases ({int((coord < 0).sum())} "
                  "inserted)")
     # ---- the baseline's items: per non-inserted base its deletion, and the four insertions behind it where a coordinate names them
-    upper = ms._UPPER[bases]
+    upper = ss._UPPER[bases]
     seq_of_base = np.repeat(np.arange(V, dtype=np.int64), np.diff(seq_offsets))
     last = np.zeros(N, dtype=bool)
     last[seq_offsets[1:][np.diff(seq_offsets) > 0] - 1] = True
@@ -98,7 +98,7 @@ def main():
     dev = torch.device("cuda", torch.cuda.current_device())
     up = lambda x, dt: torch.from_numpy(np.ascontiguousarray(x, dtype=dt)).to(dev)      # noqa: E731
     d_edits = [up(seq_offsets, np.int64), up(bases, np.uint8), up(coord, np.int32), up(pos0, np.int64), up(ref_off, np.int32),
-               up(pad(upper[dele]), np.uint8), up(alt_off, np.int32), up(pad(np.tile(ms.TO_BASES, len(ins))), np.uint8),
+               up(pad(upper[dele]), np.uint8), up(alt_off, np.int32), up(pad(np.tile(ss.TO_BASES, len(ins))), np.uint8),
                up(seq_of_base[n_of], np.int32), up(np.arange(Q), np.int32)]
     lines.append(f"baseline items: {len(dele)} deletions + {4 * len(ins)} insertions = {Q} ({Q / max(N, 1):.2f} a base)")
     ok = True
@@ -107,8 +107,8 @@ def main():
                   for k in range(n_motifs)]
         dms = [DeviceMotif.lease(m) for m in motifs]
         tables, _ = qv._weight_tables(dms, motifs, None, 1.0)
-        staged = ms._stage(tables, seq_offsets, bases, len(isc.COLUMNS))
-        new = _timed(lambda: ms._enqueue(dms, staged, False, isc.ENTRY), a.warmup, a.reps)
+        staged = ss.stage(tables, seq_offsets, bases, (N, len(isc.COLUMNS)))
+        new = _timed(lambda: ss.enqueue(dms, staged, False, isc.ENTRY), a.warmup, a.reps)
         d_tabs = [up(t.view(np.int64), np.int64) for t in tables]
         q_staged = (d_edits, d_tabs, max(int(t.max()) for t in tables), (V, Q, Q))
         rec = torch.zeros((n_motifs, Q, 4), dtype=torch.int64, device=dev)

@@ -53,6 +53,7 @@ def main():
     import torch
     from grafimo_amd import mutation_scan as ms
     from grafimo_amd import query_variants as qv
+    from grafimo_amd import sequence_scans as ss
     from grafimo_amd import synth
     from grafimo_amd.device import DeviceMotif
     from grafimo_amd.extract_regions import DeviceGraph
@@ -73,15 +74,15 @@ def main():
     hs = compute_haplotype_sequences(dg, regions, False, _Args(), classes=hc, coordinates=True)
     t2 = clock()
     prep = prepare_graphs(dg, regions, None)
-    seqs = ms._with_references(hs, prep, _matrix_rows(prep)[0])
+    seqs = ss._with_references(hs, prep, _matrix_rows(prep)[0])
     seq_offsets, bases, coord = np.ascontiguousarray(seqs[5]), np.ascontiguousarray(seqs[6]), seqs[7]
     t3 = clock()
     V, N = len(seq_offsets) - 1, len(bases)
     lines.append(f"input: {len(hs)} versions + {V - len(hs)} reference sequences = {V} sequences, {N} bases ({int((coord < 0).sum())} "
                  f"inserted); classes {t1 - t0:.2f} s, sequences {t2 - t1:.2f} s, assembling {t3 - t2:.2f} s")
     # ---- the baseline's items: three SNVs per non-inserted base
-    upper = ms._UPPER[bases]
-    column = ms._COLUMN_OF[bases]
+    upper = ss._UPPER[bases]
+    column = ss._COLUMN_OF[bases]
     at = np.flatnonzero(coord >= 0)
     n_of = np.repeat(at, 3)
     to_col = (np.tile(np.arange(3, dtype=np.int64), len(at)) + np.repeat(column[at], 3)) % 4 + 1      # the three other columns
@@ -92,15 +93,15 @@ def main():
     up = lambda x, dt: torch.from_numpy(np.ascontiguousarray(x, dtype=dt)).to(dev)      # noqa: E731
     one_each = np.arange(Q + 1, dtype=np.int32)
     d_edits = [up(seq_offsets, np.int64), up(bases, np.uint8), up(coord, np.int32), up(coord[n_of], np.int64), up(one_each, np.int32),
-               up(upper[n_of], np.uint8), up(one_each, np.int32), up(ms.TO_BASES[to_col - 1], np.uint8),
+               up(upper[n_of], np.uint8), up(one_each, np.int32), up(ss.TO_BASES[to_col - 1], np.uint8),
                up(seq_of_base[n_of], np.int32), up(np.arange(Q), np.int32)]
     for W, n_motifs in ((19, 3), (64, 1)):
         motifs = [synth.motif_object(synth.synthetic_motif(W, np.random.default_rng(7 + k), np.full(4, 0.25)), f"P{W}_{k}")
                   for k in range(n_motifs)]
         dms = [DeviceMotif.lease(m) for m in motifs]
         tables, _ = qv._weight_tables(dms, motifs, None, 1.0)
-        staged = ms._stage(tables, seq_offsets, bases)
-        new = _timed(lambda: ms._enqueue(dms, staged, False), a.warmup, a.reps)
+        staged = ss.stage(tables, seq_offsets, bases, (N, len(ms.COLUMNS)))
+        new = _timed(lambda: ss.enqueue(dms, staged, False, ms.ENTRY), a.warmup, a.reps)
         d_tabs = [up(t.view(np.int64), np.int64) for t in tables]
         q_staged = (d_edits, d_tabs, max(int(t.max()) for t in tables), (V, Q, Q))
         rec = torch.zeros((n_motifs, Q, 4), dtype=torch.int64, device=dev)

@@ -53,6 +53,7 @@ def main():
     import torch
     from grafimo_amd import _native as nv
     from grafimo_amd import mutation_scan as ms
+    from grafimo_amd import sequence_scans as ss
     from grafimo_amd import query_variants as qv
     from grafimo_amd import site_distance as sd
     from grafimo_amd import synth
@@ -72,7 +73,7 @@ def main():
     hc = compute_haplotype_classes(dg, regions, False, _Args())
     hs = compute_haplotype_sequences(dg, regions, False, _Args(), classes=hc, coordinates=True)
     prep = prepare_graphs(dg, regions, None)
-    seqs = ms._with_references(hs, prep, _matrix_rows(prep)[0])
+    seqs = ss._with_references(hs, prep, _matrix_rows(prep)[0])
     seq_offsets, bases = np.ascontiguousarray(seqs[5]), np.ascontiguousarray(seqs[6])
     V, N = len(seq_offsets) - 1, len(bases)
     lines.append(f"input: {len(hs)} versions + {V - len(hs)} reference sequences = {V} sequences, {N} bases")
@@ -96,8 +97,8 @@ def main():
                                                          cut.ctypes.data, E, 0, p_words, p_masks, status.data_ptr(), _stream_ptr(None)))
         # the mutation scan, from the same library, over the same staged sequences
         tables, _ = qv._weight_tables(dms, motifs, None, 1.0)
-        staged = ms._stage(tables, seq_offsets, bases)
-        old = _timed(lambda: ms._enqueue(dms, staged, False), a.warmup, a.reps)
+        staged = ss.stage(tables, seq_offsets, bases, (N, len(ms.COLUMNS)))
+        old = _timed(lambda: ss.enqueue(dms, staged, False, ms.ENTRY), a.warmup, a.reps)
         lines.append(f"W = {W}, {n_motifs} motifs, {N} bases: gfm_sequence_mutation_scan: median {old[0]:.3f} ms (min {old[1]:.3f}, max "
                      f"{old[2]:.3f}); {a.warmup} warm-ups, {a.reps} timed")
         for E in (1, 3, 8):
