@@ -113,7 +113,7 @@ def get_parser():
                         "haplotype's total binding affinity -- the sum of 2^(log-odds / T) over every k-mer of its own "
                         "sequence --, beside the reference's (graph routes only)")
     p.add_argument("--affinity-temperature", dest="affinity_temperature", type=float, default=None, metavar="T",
-                   help="with --haplotype-affinity, --variant-affinity, --haplotype-classes, --query-variants, --mutation-scan, --indel-scan, --deletion-scan, --substitution-scan or --shuffle-null: the temperature T > 0 the log-odds scores are "
+                   help="with --haplotype-affinity, --variant-affinity, --haplotype-classes, --query-variants, --mutation-scan, --indel-scan, --deletion-scan, --substitution-scan, --insertion-scan or --shuffle-null: the temperature T > 0 the log-odds scores are "
                         "divided by; default 1")
     p.add_argument("--variant-affinity", action="store_true", dest="variant_affinity",
                    help="also write grafimo_variant_affinity[_MOTIF].tsv (printed with -f): per variant, the log2 of the mean "
@@ -125,7 +125,7 @@ def get_parser():
                    help="also write grafimo_hit_alleles[_MOTIF].tsv (printed with -f): the report's rows, each with the variant "
                         "alleles that make its k-mer and, with --haplotype-groups, its carriers per group (graph routes only)")
     p.add_argument("--haplotype-groups", dest="haplotype_groups", metavar="FILE",
-                   help="with --hit-alleles, --hit-pairs, --haplotype-classes, --haplotype-sequences, --query-variants, --mutation-scan, --indel-scan, --deletion-scan, --substitution-scan, --site-distance or --shuffle-null: SAMPLE GROUP lines (the 1000 Genomes panel file reads as is), one "
+                   help="with --hit-alleles, --hit-pairs, --haplotype-classes, --haplotype-sequences, --query-variants, --mutation-scan, --indel-scan, --deletion-scan, --substitution-scan, --insertion-scan, --site-distance or --shuffle-null: SAMPLE GROUP lines (the 1000 Genomes panel file reads as is), one "
                         "haplotypes_GROUP column per group")
     p.add_argument("--haplotype-classes", action="store_true", dest="haplotype_classes",
                    help="also write grafimo_haplotype_classes[_MOTIF].tsv (printed with -f) and "
@@ -198,6 +198,18 @@ def get_parser():
                    help="with --substitution-scan: also keep the rows with |delta_log2_affinity| >= X")
     p.add_argument("--substitution-all", action="store_true", dest="substitution_all",
                    help="with --substitution-scan: keep every row, up to one per base and length")
+    p.add_argument("--insertion-scan", dest="insertion_scan", nargs="+", default=None, metavar="SEQ",
+                   help="also write grafimo_insertion_scan[_MOTIF].tsv and grafimo_insertion_scan_summary[_MOTIF].tsv (printed "
+                        "with -f): the deletion scan's companion for block insertions -- each given SEQ, 1 .. 16 inserts of "
+                        "1 .. 64 letters of ACGT (case is folded, a repeated SEQ is dropped), inserted behind every base of "
+                        "every sequence the haplotypes spell in a region (inserted bases too) and of the reference sequence, "
+                        "with the best hit and the total affinity before and after, the effect, and the haplotypes that spell "
+                        "the sequence, in all and per --haplotype-groups group; rows are kept on gain or loss; in a repeat an "
+                        "insertion is reported once, at its leftmost offset (graph routes only)")
+    p.add_argument("--insertion-delta", dest="insertion_delta", type=float, default=None, metavar="X",
+                   help="with --insertion-scan: also keep the rows with |delta_log2_affinity| >= X")
+    p.add_argument("--insertion-all", action="store_true", dest="insertion_all",
+                   help="with --insertion-scan: keep every row, up to one per base and insert")
     p.add_argument("--site-distance", dest="site_distance", nargs="?", type=int, const=3, default=None, metavar="E",
                    help="also write grafimo_site_distance[_MOTIF].tsv and grafimo_site_distance_summary[_MOTIF].tsv (printed "
                         "with -f): for every window of every sequence the haplotypes spell in a region (inserted bases too) and "
@@ -300,7 +312,8 @@ _GRAPH_TABLES = {"variant_effects": ("--variant-effects", "alleles"), "haplotype
                  "haplotype_sequences": ("--haplotype-sequences", "haplotypes"),
                  "query_variants": ("--query-variants", "haplotypes"), "mutation_scan": ("--mutation-scan", "haplotypes"),
                  "indel_scan": ("--indel-scan", "haplotypes"), "deletion_scan": ("--deletion-scan", "haplotypes"),
-                 "substitution_scan": ("--substitution-scan", "haplotypes"), "site_distance": ("--site-distance", "haplotypes"),
+                 "substitution_scan": ("--substitution-scan", "haplotypes"), "insertion_scan": ("--insertion-scan", "haplotypes"),
+                 "site_distance": ("--site-distance", "haplotypes"),
                  "shuffle_null": ("--shuffle-null", "haplotypes")}
 
 
@@ -341,7 +354,7 @@ def main(argv=None):
     _graph_only(a, "haplotype_scores")
     if a.affinity_temperature is not None and not (a.haplotype_affinity or a.variant_affinity or a.haplotype_classes
                                                     or a.query_variants or a.mutation_scan or a.indel_scan or a.deletion_scan
-                                                    or a.substitution_scan or a.shuffle_null):
+                                                    or a.substitution_scan or a.insertion_scan or a.shuffle_null):
         sys.exit("ERROR: --affinity-temperature goes with --haplotype-affinity or --variant-affinity or --haplotype-classes")
     if a.affinity_temperature is not None and not a.affinity_temperature > 0:
         sys.exit(f"ERROR: --affinity-temperature {a.affinity_temperature} is not > 0")
@@ -353,7 +366,7 @@ def main(argv=None):
     _graph_only(a, "variant_affinity")
     if a.haplotype_groups and not (a.hit_alleles or a.hit_pairs or a.haplotype_classes or a.haplotype_sequences
                                    or a.query_variants or a.mutation_scan or a.indel_scan or a.deletion_scan
-                                   or a.substitution_scan or a.site_distance or a.shuffle_null):
+                                   or a.substitution_scan or a.insertion_scan or a.site_distance or a.shuffle_null):
         sys.exit("ERROR: --haplotype-groups goes with --hit-alleles or --hit-pairs or --haplotype-classes or "
                  "--haplotype-sequences or --site-distance")
     if a.class_min_haplotypes is not None and not a.haplotype_classes:
@@ -414,6 +427,19 @@ def main(argv=None):
         except ValueError as e:
             sys.exit(f"ERROR: --substitution-map: {e}")
     _graph_only(a, "substitution_scan")
+    if a.insertion_all and not a.insertion_scan:
+        sys.exit("ERROR: --insertion-all goes with --insertion-scan")
+    if a.insertion_delta is not None and not a.insertion_scan:
+        sys.exit("ERROR: --insertion-delta goes with --insertion-scan")
+    if a.insertion_delta is not None and not a.insertion_delta >= 0:
+        sys.exit(f"ERROR: --insertion-delta {a.insertion_delta} is not >= 0")
+    if a.insertion_scan:
+        from .insertion_scan import checked_inserts
+        try:
+            a.insertion_scan = list(checked_inserts(list(dict.fromkeys(s.upper() for s in a.insertion_scan))))
+        except ValueError as e:
+            sys.exit(f"ERROR: --insertion-scan: {e}")
+    _graph_only(a, "insertion_scan")
     if a.site_distance_all and a.site_distance is None:
         sys.exit("ERROR: --site-distance-all goes with --site-distance")
     if a.site_distance is not None and not 1 <= a.site_distance <= 8:
@@ -629,6 +655,8 @@ def main(argv=None):
              dict(temperature=temperature, delta=a.deletion_delta, all_rows=a.deletion_all)),
             (a.substitution_scan, "substitution_scan", "substitution scan", (a.substitution_scan, a.substitution_map or "transversion"),
              dict(temperature=temperature, delta=a.substitution_delta, all_rows=a.substitution_all)),
+            (a.insertion_scan, "insertion_scan", "insertion scan", (a.insertion_scan,),
+             dict(temperature=temperature, delta=a.insertion_delta, all_rows=a.insertion_all)),
             (a.site_distance is not None, "site_distance", "site distance", (),
              dict(max_edits=a.site_distance, all_rows=a.site_distance_all))):
         if not asked:

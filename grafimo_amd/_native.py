@@ -46,6 +46,9 @@ GFM_DELSCAN_TILE = 64          # (as GFM_MUTSCAN_TILE)
 GFM_DELSCAN_MAX_LENGTH = 64    # (the deletion scan's longest block: GFM_QUERY_MAX_ALLELE, and what the key's rel field holds)
 GFM_SUBSCAN_TILE = 64          # (as GFM_MUTSCAN_TILE)
 GFM_SUBSCAN_MAX_LENGTH = 64    # (the substitution scan's longest block: as GFM_DELSCAN_MAX_LENGTH)
+GFM_INSSCAN_TILE = 64          # (as GFM_MUTSCAN_TILE)
+GFM_INSSCAN_MAX_LENGTH = 64    # (the insertion scan's longest insert: as GFM_DELSCAN_MAX_LENGTH)
+GFM_INSSCAN_MAX_INSERTS = 16   # (the insertion scan's longest list of inserts)
 GFM_SITEDIST_TILE = 64         # (as GFM_MUTSCAN_TILE)
 GFM_SITEDIST_MAX_EDITS = 8     # (the site distance's largest cap E: d = E + 1 fits a word's four bits)
 GFM_NULL_LDS_BASES = 960      # (the shuffle null's longest sequence shuffled in the LDS: exported for tests that aim at its edge)
@@ -182,6 +185,8 @@ PROTOTYPES = {
                                            ctypes.c_uint32, c_void_p, c_void_p, c_void_p, c_void_p]),
     "gfm_sequence_substitution_scan": (c_int, [c_void_p, c_i32, c_void_p, c_u64, c_i32, c_void_p, c_void_p, c_i32, c_void_p, c_void_p,
                                                ctypes.c_uint32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "gfm_sequence_insertion_scan": (c_int, [c_void_p, c_i32, c_void_p, c_u64, c_i32, c_void_p, c_void_p, c_i32, c_void_p, c_void_p,
+                                            ctypes.c_uint32, c_void_p, c_void_p, c_void_p, c_void_p]),
     "gfm_sequence_site_distance": (c_int, [c_void_p, c_i32, c_i32, c_void_p, c_void_p, c_void_p, c_i32, ctypes.c_uint32, c_void_p,
                                            c_void_p, c_void_p, c_void_p]),
     "gfm_sequence_shuffle_null": (c_int, [c_void_p, c_i32, c_void_p, c_u64, c_i32, c_void_p, c_void_p, c_void_p, c_void_p, c_i32,

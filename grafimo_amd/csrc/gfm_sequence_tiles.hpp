@@ -1,5 +1,5 @@
 // gfm_sequence_tiles.hpp -- what the tile-based sequence scans share (included at the end of graph_extract.hip ahead of
-// gfm_graph_mutation_scan.hpp; the mutation, indel, deletion and substitution scans and the site distance build on it; it
+// gfm_graph_mutation_scan.hpp; the mutation, indel, deletion, substitution and insertion scans and the site distance build on it; it
 // uses gfail, GX_TRY, align256, kSeqMotifs and gfm_graph_table_score.hpp's StrandScores and edit_key).  The shuffle null is
 // not among them: its entry lists sequences by length class, not by tile.
 //   host    the tile table of a call from its seq_offsets (seq_tiles), the length list as a mask (length_mask), the checks of
@@ -9,7 +9,7 @@
 //           in the order its tests pin.
 //   device  the tile's bounds check (seq_tile_bad), the staging of a motif's packed table (stage_table), the best key and the
 //           sum of one side (SideBest), and the COVER column of the two block scans (cover_head, cover_extend): the indel,
-//           deletion and substitution kernels call them.  The mutation and the site-distance kernel keep their own copies
+//           deletion, substitution and insertion kernels call them.  The mutation and the site-distance kernel keep their own copies
 //           of the first two: they measured slower with these (profiles/sequence_scan_refactor.txt), and their device code
 //           is what it was.
 namespace {

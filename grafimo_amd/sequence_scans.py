@@ -1,6 +1,6 @@
-"""What the sequence scans share: mutation_scan, indel_scan, deletion_scan, substitution_scan and site_distance, and the shuffle
-null where it scans the same sequences.  Each of those modules keeps its own RULE, its cells and its frames' own columns; here is
-what was the same in all of them:
+"""What the sequence scans share: mutation_scan, indel_scan, deletion_scan, substitution_scan, insertion_scan and site_distance, and
+the shuffle null where it scans the same sequences.  Each of those modules keeps its own RULE, its cells and its frames' own
+columns; here is what was the same in all of them:
   the sequences   the checked plain arrays (_checked_sequences), the versions of a region with its reference sequence
                   (_with_references), and the prologue of every compute_*_many (scan_inputs);
   the kernel      the staging and the call of an entry that writes keys and sums (stage, enqueue, scan -- the probes time the

@@ -998,6 +998,53 @@ int gfm_sequence_substitution_scan(const gfm_motif_t *motifs, int32_t n_motifs, 
                                    int32_t n_lengths, const int32_t *lengths, const uint8_t base_map[4], uint32_t flags,
                                    uint32_t *const *d_keys, uint64_t *const *d_sums, int32_t *d_status, void *stream);
 
+/* ------------------------------------------------------------------ insertion scan: given inserts of 1 .. 64 bases behind every base of a spelled sequence
+ * Graph-independent.  THE RULE.  For a sequence x of n bases, a motif of width W, a list of K inserts with K in 1 .. 16, every
+ * insert I of the list, Li its length in 1 .. 64, and every offset o in 0 .. n - 1:
+ *   Every insert holds A, C, G, T only.  Case is folded, as base_code does.
+ *   The edit is the insertion of I behind x[o].  Let o' = o + 1 and y = x[:o'] + I + x[o':].
+ *   This is gfm_graph_query_edits' rule with lr = 0, la = Li at offset o'.
+ *     REF side (column JUNCTION): the starts s of x across the junction, max(0, o' - W + 1) <= s <= min(o' - 1, n - W).
+ *     It does not depend on the insert.  It equals the indel scan's JUNCTION column bit for bit.
+ *     ALT side (column INS): the starts s of y with max(0, o' - W + 1) <= s <= min(o' + Li - 1, n + Li - W).
+ *     A window that lies wholly inside the insert counts, as the query rule counts it.
+ *   Every window is scored once per strand, or + only under GFM_GRAPH_FORWARD_ONLY.
+ *   A window that holds a base of x that is not A/C/G/T scores min_val on both strands.
+ *   An insertion repairs nothing, because it removes no base.  A window that does not reach the N is clean.
+ *   Per column, the best window by (score descending, s ascending, + before -), as the key
+ *   ((score + 1) << 8) | ((64 - (s - o')) << 1) | plus, s - o' in -(W - 1) .. -1 for JUNCTION and in -(W - 1) .. Li - 1 for INS.
+ *   Key 0 means the side has no window.
+ *   Per column, the exact uint64 sum of w[score] over the side's windows and strands.
+ *   An insertion before the first base of a sequence is not scanned, as in the indel scan.  An empty sequence has no rows.
+ *   With the inserts ("A", "C", "G", "T") the INS columns equal the indel scan's INS_A .. INS_T bit for bit.
+ *   A cell does not depend on the other inserts of the list or on their order.
+ * By construction a cell equals, field for field, what gfm_graph_query_edits returns for the insertion (coordinate of o + 1,
+ * "", I) applied to x, wherever coordinates can name the gap (GFM_QUERY_MAX_ALLELE is 64 as well, and the key's 7-bit field
+ * holds every s - o' that occurs).
+ *
+ * The arguments are gfm_sequence_indel_scan's and the inserts: n_inserts in 1 .. GFM_INSSCAN_MAX_INSERTS, insert_offsets int32
+ * [n_inserts + 1] on the HOST, starting at 0 and ascending, and insert_bases uint8 [insert_offsets[n_inserts]] on the HOST:
+ * insert i is insert_bases[insert_offsets[i] .. insert_offsets[i + 1]), 1 .. GFM_INSSCAN_MAX_LENGTH letters of ACGTacgt.
+ * Exactly those counts are read.  The library does not compare the inserts with each other.  Refused when max_weight * 2 *
+ * (W + Lmax - 1) passes 2^64 - 1, Lmax the longest insert: an ALT side has at most W + Lmax - 1 windows.  d_keys[m] uint32
+ * [n_inserts][seq_offsets[n_seqs]][2], 8-byte aligned, and d_sums[m] uint64 of the same shape, 16-byte aligned: per insert and
+ * base of d_bases the columns JUNCTION, INS (JUNCTION is the same for every insert).  Every cell is written, nothing is zeroed
+ * by the caller.  The work is cut into (sequence, GFM_INSSCAN_TILE offsets) tiles by the library; the result does not depend
+ * on the tile -- it is exported only so that tests can aim at its edges.  No sequence or no base returns GFM_OK and touches
+ * nothing.  GFM_ERR_INVALID, all before anything is launched, in this order: n_motifs < 1, n_seqs < 0 or n_inserts outside
+ * 1 .. GFM_INSSCAN_MAX_INSERTS; an unknown flag; NULL insert_offsets or insert_bases, insert_offsets that do not start at 0 or
+ * that descend; a length outside 1 .. GFM_INSSCAN_MAX_LENGTH; a letter outside ACGTacgt -- these with no sequence too --; then
+ * offsets that descend, a sequence of 2^31 bases or more, a NULL pointer, a misaligned result, motifs of different widths or on
+ * another device than the current one, weights that can overflow a sum.  The call WAITS for the stream (it reads the verdict
+ * of the device's check of the tile table). */
+#define GFM_INSSCAN_TILE 64
+#define GFM_INSSCAN_MAX_LENGTH 64
+#define GFM_INSSCAN_MAX_INSERTS 16
+int gfm_sequence_insertion_scan(const gfm_motif_t *motifs, int32_t n_motifs, const uint64_t *const *d_weights, uint64_t max_weight,
+                                int32_t n_seqs, const int64_t *seq_offsets, const uint8_t *d_bases, int32_t n_inserts,
+                                const int32_t *insert_offsets, const uint8_t *insert_bases, uint32_t flags,
+                                uint32_t *const *d_keys, uint64_t *const *d_sums, int32_t *d_status, void *stream);
+
 /* ------------------------------------------------------------------ site distance: substitutions from a site, for every window of a spelled sequence
  * Graph-independent.  THE RULE.
  * Inputs: a sequence x of n bases; a motif of width W with its integer matrix as the packed table holds it, entry t[j][b] for
