@@ -159,6 +159,17 @@ def get_parser():
                    help="with --mutation-scan: also keep the rows with |delta_log2_affinity| >= X")
     p.add_argument("--mutation-all", action="store_true", dest="mutation_all",
                    help="with --mutation-scan: keep every row, three per base")
+    p.add_argument("--mutation-profile", action="store_true", dest="mutation_profile",
+                   help="also write grafimo_mutation_profile.tsv and grafimo_mutation_profile_summary.tsv (printed with -f): the "
+                        "mutation scan folded over the whole motif set on the GPU -- per single-base change how many motifs "
+                        "gain and lose a site (p < -t), the most significant gain and loss, and the motifs whose total "
+                        "affinity (--affinity-temperature) moves most, up and down; a row carries its sequence's "
+                        "haplotypes, also per --haplotype-groups group; one table per call; rows are kept when some motif gains or loses "
+                        "(graph routes only)")
+    p.add_argument("--mutation-profile-delta", dest="mutation_profile_delta", type=float, default=None, metavar="X",
+                   help="with --mutation-profile: also keep the rows whose up or down champion has |delta_log2_affinity| >= X")
+    p.add_argument("--mutation-profile-all", action="store_true", dest="mutation_profile_all",
+                   help="with --mutation-profile: keep every row, three per base")
     p.add_argument("--indel-scan", action="store_true", dest="indel_scan",
                    help="also write grafimo_indel_scan[_MOTIF].tsv and grafimo_indel_scan_summary[_MOTIF].tsv (printed with "
                         "-f): the mutation scan's companion for one-base indels -- the deletion of every base and the insertion "
@@ -311,6 +322,7 @@ _GRAPH_TABLES = {"variant_effects": ("--variant-effects", "alleles"), "haplotype
                  "haplotype_classes": ("--haplotype-classes", "haplotypes"),
                  "haplotype_sequences": ("--haplotype-sequences", "haplotypes"),
                  "query_variants": ("--query-variants", "haplotypes"), "mutation_scan": ("--mutation-scan", "haplotypes"),
+                 "mutation_profile": ("--mutation-profile", "haplotypes"),
                  "indel_scan": ("--indel-scan", "haplotypes"), "deletion_scan": ("--deletion-scan", "haplotypes"),
                  "substitution_scan": ("--substitution-scan", "haplotypes"), "insertion_scan": ("--insertion-scan", "haplotypes"),
                  "site_distance": ("--site-distance", "haplotypes"),
@@ -353,8 +365,8 @@ def main(argv=None):
     _graph_only(a, "haplotype_hits")
     _graph_only(a, "haplotype_scores")
     if a.affinity_temperature is not None and not (a.haplotype_affinity or a.variant_affinity or a.haplotype_classes
-                                                    or a.query_variants or a.mutation_scan or a.indel_scan or a.deletion_scan
-                                                    or a.substitution_scan or a.insertion_scan or a.shuffle_null):
+                                                    or a.query_variants or a.mutation_scan or a.mutation_profile or a.indel_scan
+                                                    or a.deletion_scan or a.substitution_scan or a.insertion_scan or a.shuffle_null):
         sys.exit("ERROR: --affinity-temperature goes with --haplotype-affinity or --variant-affinity or --haplotype-classes")
     if a.affinity_temperature is not None and not a.affinity_temperature > 0:
         sys.exit(f"ERROR: --affinity-temperature {a.affinity_temperature} is not > 0")
@@ -365,8 +377,8 @@ def main(argv=None):
         sys.exit(f"ERROR: --variant-affinity-delta {a.variant_affinity_delta} is not >= 0")
     _graph_only(a, "variant_affinity")
     if a.haplotype_groups and not (a.hit_alleles or a.hit_pairs or a.haplotype_classes or a.haplotype_sequences
-                                   or a.query_variants or a.mutation_scan or a.indel_scan or a.deletion_scan
-                                   or a.substitution_scan or a.insertion_scan or a.site_distance or a.shuffle_null):
+                                   or a.query_variants or a.mutation_scan or a.mutation_profile or a.indel_scan
+                                   or a.deletion_scan or a.substitution_scan or a.insertion_scan or a.site_distance or a.shuffle_null):
         sys.exit("ERROR: --haplotype-groups goes with --hit-alleles or --hit-pairs or --haplotype-classes or "
                  "--haplotype-sequences or --site-distance")
     if a.class_min_haplotypes is not None and not a.haplotype_classes:
@@ -389,6 +401,13 @@ def main(argv=None):
     if a.mutation_delta is not None and not a.mutation_delta >= 0:
         sys.exit(f"ERROR: --mutation-delta {a.mutation_delta} is not >= 0")
     _graph_only(a, "mutation_scan")
+    if a.mutation_profile_all and not a.mutation_profile:
+        sys.exit("ERROR: --mutation-profile-all goes with --mutation-profile")
+    if a.mutation_profile_delta is not None and not a.mutation_profile:
+        sys.exit("ERROR: --mutation-profile-delta goes with --mutation-profile")
+    if a.mutation_profile_delta is not None and not a.mutation_profile_delta >= 0:
+        sys.exit(f"ERROR: --mutation-profile-delta {a.mutation_profile_delta} is not >= 0")
+    _graph_only(a, "mutation_profile")
     if a.indel_all and not a.indel_scan:
         sys.exit("ERROR: --indel-all goes with --indel-scan")
     if a.indel_delta is not None and not a.indel_scan:
@@ -670,6 +689,17 @@ def main(argv=None):
         if not a.text_only:
             for motif, t in zip(motifs, tables):
                 print(f"{len(t.summary_frame())} {noun} summary rows written to {write_summary(t, motif, len(motifs), wf)}")
+    if a.mutation_profile:                             # (one table per call: the scan folded over the motif set)
+        from .mutation_profile import (compute_mutation_profile, print_mutation_profile, write_mutation_profile,
+                                       write_mutation_profile_summary)
+        graph, regions, first_index = source("mutation_profile")
+        mp = compute_mutation_profile(motifs, graph, regions, a.debug, wf, haplotype_groups=groups(first_index),
+                                      temperature=temperature, delta=a.mutation_profile_delta, all_rows=a.mutation_profile_all)
+        if a.text_only:                                # -f: printed like the report, no file written
+            print_mutation_profile(mp)
+        else:
+            print(f"{len(mp)} mutation profile rows written to {write_mutation_profile(mp, wf)}")
+            print(f"{len(mp.summary_frame())} mutation profile summary rows written to {write_mutation_profile_summary(mp, wf)}")
     if a.shuffle_null is not None:                     # (a table per motif, and one row per motif for the whole call)
         from .shuffle_null import (compute_shuffle_null_many, print_motif_enrichment, print_shuffle_null, write_motif_enrichment,
                                    write_shuffle_null)

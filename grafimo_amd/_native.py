@@ -189,6 +189,8 @@ PROTOTYPES = {
                                             ctypes.c_uint32, c_void_p, c_void_p, c_void_p, c_void_p]),
     "gfm_sequence_site_distance": (c_int, [c_void_p, c_i32, c_i32, c_void_p, c_void_p, c_void_p, c_i32, ctypes.c_uint32, c_void_p,
                                            c_void_p, c_void_p, c_void_p]),
+    "gfm_scan_fold": (c_int, [c_i32, c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_i32, c_i32, c_void_p, c_void_p, c_void_p,
+                              c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "gfm_sequence_shuffle_null": (c_int, [c_void_p, c_i32, c_void_p, c_u64, c_i32, c_void_p, c_void_p, c_void_p, c_void_p, c_i32,
                                           c_u64, c_void_p, ctypes.c_uint32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                           c_void_p, c_void_p, c_void_p, c_void_p]),

@@ -2652,3 +2652,4 @@ inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 #include "gfm_graph_site_distance.hpp"
 #include "gfm_graph_shuffle_null.hpp"
 #include "gfm_graph_insertion_scan.hpp"
+#include "gfm_scan_fold.hpp"

@@ -1096,6 +1096,49 @@ int gfm_sequence_site_distance(const gfm_motif_t *motifs, int32_t n_motifs, int3
                                const uint8_t *d_bases, const int32_t *cutoffs, int32_t max_edits, uint32_t flags,
                                uint32_t *const *d_words, uint64_t *const *d_masks, int32_t *d_status, void *stream);
 
+/* ------------------------------------------------------------------ scan fold: a motif set's gains, losses and champions per cell
+ * The fold over the motif axis of what any keys/sums scan entry leaves: the dense per-motif arrays stay on the device, and a
+ * running state per (row, pair of columns) keeps counts and champions of the whole motif set.  THE RULE.
+ * Inputs of one call: n_motifs >= 1 motifs; motif m has a caller-given id motif_ids[m] >= 0, distinct within the call, a score
+ * cutoff cutoffs[m] in 0 .. table_lens[m], a device tail table d_ptables[m] float64 [table_lens[m]], and d_keys[m] uint32
+ * [n_rows][n_columns] and d_sums[m] uint64 [n_rows][n_columns] as a scan entry leaves them; n_pairs in 1 .. 8 pairs
+ * (ref_column, alt_column) on the HOST, int32 [n_pairs][2], columns in 0 .. n_columns - 1, ref != alt, n_columns in 2 .. 8.
+ * For every (row, pair) and every motif, with r, a the two keys' scores (key >> 8) - 1 (-1 for key 0) and R, A the two sums:
+ *   A side is a site when its key is not 0 and its score >= cutoff: what gfm_motif_pvalue_cutoff means.
+ *   gain when a is a site and r is not.  loss when r is a site and a is not.
+ *   counts[gain] and counts[loss] count the motifs.
+ *   Gain champion: the gaining motif with the smallest ptable[a].  Loss champion: the losing motif with the smallest ptable[r].
+ *   Ties go to the smaller motif id.  Doubles are compared as doubles; nothing is recomputed.
+ *   The state keeps the champion's id, its two keys and that p.
+ *   A score >= table_len reads entry table_len - 1: nothing is read outside a table.
+ *   Up champion: among motifs with A > R, the one with the largest A / R, compared exactly.  Motif 1 beats motif 2 when
+ *   A1 * R2 > A2 * R1 in 128-bit unsigned arithmetic.  This holds for R = 0 too: an infinite ratio beats a finite one, and
+ *   two infinite ones tie.  Ties go to the smaller id.
+ *   Down champion: among A < R, the largest R / A by the same rule.  The state keeps the id and both sums.
+ *   The state is a running one: folding motif sets S1 then S2 into the same state gives what folding their union in one call
+ *   gives, in any order and any split.
+ *   The empty state is all zero bytes.  Ids are stored as id + 1, and the caller zeroes the arrays once.
+ *   Folding the same id twice into a state is the caller's error and is not detected.
+ * The state, a struct of arrays, per (row, pair) 88 bytes, P = n_pairs:
+ *   d_counts      uint32  [n_rows][P][2]       gain, loss
+ *   d_site_motif  uint32  [n_rows][P][2]       gain, loss: id + 1, 0: none
+ *   d_site_keys   uint32  [n_rows][P][2][2]    (ref key, alt key) of the gain and of the loss champion
+ *   d_site_p      float64 [n_rows][P][2]
+ *   d_aff_motif   uint32  [n_rows][P][2]       up, down: id + 1, 0: none
+ *   d_aff_sums    uint64  [n_rows][P][2][2]    (ref sum, alt sum) of the up and of the down champion
+ * The intended pairs: the mutation scan's (0,1) (0,2) (0,3) (0,4) over 5 columns; the indel scan's (0,1) (2,3) (2,4) (2,5)
+ * (2,6) over 7; the block scans' (0,1) over their (COVER, ALT) cells with n_rows = n_lengths * n_bases.
+ * GFM_ERR_INVALID, all before any device work: n_motifs < 1, n_rows outside 0 .. 2^40, n_columns outside 2 .. 8, n_pairs outside
+ * 1 .. 8; then, with rows, a NULL pointer, a pair outside its columns or with ref == alt, a negative or repeated id (or the id
+ * 2^31 - 1, which id + 1 cannot hold), table_len < 1, a cutoff outside 0 .. table_len, d_sums[m], d_ptables[m], d_site_p or
+ * d_aff_sums that are not 8-byte aligned.  n_rows == 0 returns GFM_OK and touches nothing.
+ * The kernels (one per 16 motifs) are enqueued on `stream`, behind whatever wrote the keys and sums there.  Unlike the scan
+ * entries the call does NOT wait for the stream: it has no verdict to read.  The host arrays are read before it returns. */
+int gfm_scan_fold(int32_t n_motifs, const int32_t *motif_ids, const int32_t *cutoffs, const double *const *d_ptables,
+                  const int32_t *table_lens, int64_t n_rows, int32_t n_columns, int32_t n_pairs, const int32_t *pairs,
+                  const uint32_t *const *d_keys, const uint64_t *const *d_sums, uint32_t *d_counts, uint32_t *d_site_motif,
+                  uint32_t *d_site_keys, double *d_site_p, uint32_t *d_aff_motif, uint64_t *d_aff_sums, void *stream);
+
 /* ------------------------------------------------------------------ shuffle null: empirical p-values for best score and total affinity
  * Graph-independent.  THE RULE.  All arithmetic on 64-bit words is modulo 2^64.
  *   G = 0x9E3779B97F4A7C15.
